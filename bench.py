@@ -10,14 +10,20 @@ Weights are random-init (seeded) ResNet-50 v1.5 of the full architecture.
 Data parallel, weak scaling: each rank runs its own per-GPU batch; the value is the
 WHOLE-JOB images/sec = world * batch * steps / max_rank_elapsed.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed
+steps, the optional output dump, one JSON line.  ``--full`` adds everything else the
+benchmark measures, after the headline and untimed for it: the ResNet-50 edge latency
+points (``extra.edge``), the YOLOv8n figure (``extra.yolov8n``), and on one GPU the
+replica digest check (C4, which only a multi-GPU job needs).
 
 Without a launcher (no WORLD_SIZE in the env) ``--gpus N>1`` makes this process a
 launcher: it counts devices (no HIP initialisation), spawns N fresh ranks of itself
 with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, and exits with the first failing rank's
-code.  After the timed loop every rank replays one batch of frames from a SHARED seed
-and the ranks compare digests of the pre-softmax logits (C4): a replica whose
+code.  After the timed loop of a multi-GPU job every rank replays one batch of frames from
+a SHARED seed and the ranks compare digests of the pre-softmax logits (C4): a replica whose
 weights or kernels drifted fails the run instead of silently skewing it.
 """
 from __future__ import annotations
@@ -70,12 +76,20 @@ def main(argv=None):
                     default=float(os.environ.get("KVEDGE_LAUNCH_TIMEOUT", 1500)),
                     help="self-launch (--gpus N > 1 without torchrun): kill every rank after "
                          "this many seconds (a hung RCCL init must not hang the job)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline (untimed for it) also run what a plain run leaves "
+                         "out: the edge latency points (--edge), the YOLOv8n figure (--yolo) and, "
+                         "on one GPU, the replica digest check (extra.replica_check)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the timed path returned in "
+                         "its last step as DIR/<name>.npy (float32 / float64, rank 0; an output "
+                         "over the size cap is stored as a fixed seeded sample)")
     ap.add_argument("--edge", default=os.environ.get("KVEDGE_EDGE", "1,8,64"),
-                    help="ResNet-50: after the headline (untimed for it), p50/p99 latency at "
-                         "these edge batch sizes -> extra.edge ('' = skip)")
+                    help="--full, ResNet-50: after the headline (untimed for it), p50/p99 latency "
+                         "at these edge batch sizes -> extra.edge ('' = skip)")
     ap.add_argument("--yolo", type=int, default=int(os.environ.get("KVEDGE_BENCH_YOLO", 1)),
-                    help="ResNet-50 run: after the headline and the edge block (untimed for "
-                         "them), also time YOLOv8n + decode + NMS at its bench config "
+                    help="--full, ResNet-50 run: after the headline and the edge block (untimed "
+                         "for them), also time YOLOv8n + decode + NMS at its bench config "
                          "(engine.BENCH_BATCH / BENCH_STREAMS) -> extra.yolov8n (0 = skip)")
     ap.add_argument("--perturb-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--hang-rank", type=int, default=-1, help=argparse.SUPPRESS)
@@ -177,17 +191,23 @@ def main(argv=None):
     hip_graph, n_streams = eng.graph is not None, eng.n_streams
     # C3: job time = slowest rank
     (max_elapsed,) = parallel.allreduce_scalars([elapsed], op="max")
-    # C4 (untimed): every rank runs the same frames (shared seed, not seed+rank) through
-    # its own weights/kernels; digests of the pre-softmax outputs must agree
-    with torch.no_grad():
-        ops.synth_frames(eng.frames, a.seed, 0)
-        raw_out = model.raw_outputs(eng.frames)
-        local = parallel.digest(raw_out)
-    sync()
-    rc = parallel.check_replicas(local)
-    del raw_out
+    if a.dump_outputs and di.is_main:
+        # the last timed step's outputs, before anything below touches the device again
+        _dump_outputs(a.dump_outputs, a.model, eng.outputs, a.seed)
+    rc = None
+    if a.full or di.world_size > 1:
+        # C4 (untimed): every rank runs the same frames (shared seed, not seed+rank) through
+        # its own weights/kernels; digests of the pre-softmax outputs must agree.  A plain
+        # one-GPU run has no second replica to compare with and leaves it out
+        with torch.no_grad():
+            ops.synth_frames(eng.frames, a.seed, 0)
+            raw_out = model.raw_outputs(eng.frames)
+            local = parallel.digest(raw_out)
+        sync()
+        rc = parallel.check_replicas(local)
+        del raw_out
     edge = None
-    if on_gpu and a.model == "resnet50" and a.edge.strip():
+    if a.full and on_gpu and a.model == "resnet50" and a.edge.strip():
         # the module's real operating points (twin batch, default 64), after the headline
         # timing and the C4 check so neither can be distorted by it
         from kvedge_amd.engine import edge_latency
@@ -196,7 +216,7 @@ def main(argv=None):
                             device=di.device, seed=a.seed + di.rank)
 
     yolo = None
-    if on_gpu and a.model == "resnet50" and a.yolo:
+    if a.full and on_gpu and a.model == "resnet50" and a.yolo:
         # BASELINE.json config 4 under the same clock discipline as the headline: fresh
         # engine at its own bench config, W untimed warmup steps, K timed steps bracketed
         # by barrier + synchronize, slowest rank's time (the ResNet-50 engine stays
@@ -240,8 +260,8 @@ def main(argv=None):
             "build_s": round(build_s, 2),
             "prepare_s": {k: round(v, 2) for k, v in (getattr(eng, "prep_s", None) or {}).items()},
             "graph_refine": getattr(eng, "refine", None),
-            "replica_check": {"ok": rc.ok, "max_rel_dev": rc.max_rel_dev,
-                              "digests": rc.digests},
+            "replica_check": ({"ok": rc.ok, "max_rel_dev": rc.max_rel_dev,
+                               "digests": rc.digests} if rc is not None else None),
             "backend": di.backend,
             "timed_loop": "native" if lat_hist is not None else "python",
         },
@@ -255,7 +275,7 @@ def main(argv=None):
         res["extra"]["step_latency_ms"] = {k: round(v, 4) for k, v in lat_hist.summary().items()}
     if di.is_main:
         log_event(log, "timed", steps=a.steps, ms_per_step=res["ms_per_step"],
-                  value=res["value"], replica_ok=rc.ok)
+                  value=res["value"], replica_ok=rc.ok if rc is not None else None)
         line = json.dumps(res)
         print(line, flush=True)
         if a.json_out:
@@ -269,11 +289,44 @@ def main(argv=None):
         print(f"# eager-step profile -> {a.profile}: total {prof['total_ms']:.2f} ms; "
               + ", ".join(f"{k} {v:.2f}" for k, v in top), file=sys.stderr)
     parallel.shutdown()
-    if not rc.ok:
+    if rc is not None and not rc.ok:
         print(f"replica check FAILED: max relative deviation {rc.max_rel_dev:.3e} "
               f"(digests {rc.digests})", file=sys.stderr)
         return 3
     return 0
+
+
+OUTPUT_NAMES = {"resnet50": ("probs", "top1"), "yolov8n": ("detections", "count")}
+DUMP_MAX_BYTES = 60_000_000  # array data of one dump, all files together (under 64 MB on disk)
+
+
+def _dump_outputs(out_dir, model_name, outputs, seed):
+    """Write the step outputs (a tensor or a tuple of tensors) as ``out_dir/<name>.npy``:
+    float32, or float64 for 64-bit dtypes so integer results stay exact.  YOLOv8n: rows of
+    ``detections`` past an image's ``count`` are not results and are stored as zeros.  An
+    array over its share of DUMP_MAX_BYTES is stored as a sample of its flattened elements
+    at indices drawn once from ``seed`` (sorted, the same for every run of these arguments)."""
+    import numpy as np
+    import torch
+
+    outs = (outputs,) if isinstance(outputs, torch.Tensor) else tuple(outputs)
+    names = OUTPUT_NAMES[model_name]
+    names = names if len(names) == len(outs) else tuple(f"out{i}" for i in range(len(outs)))
+    host = [t.detach().cpu() for t in outs]
+    if model_name == "yolov8n" and len(host) == 2:
+        det, cnt = host
+        live = torch.arange(det.shape[1])[None, :] < cnt.long()[:, None]
+        host[0] = torch.where(live[..., None], det, torch.zeros((), dtype=det.dtype))
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(host)
+    for name, t in zip(names, host):
+        wide = t.dtype in (torch.float64, torch.int64)
+        arr = t.to(torch.float64 if wide else torch.float32).numpy()
+        cap = share // arr.itemsize
+        if arr.size > cap:
+            idx = np.sort(np.random.default_rng(seed).choice(arr.size, size=cap, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def _time_yolo(a, di, sync):

@@ -33,7 +33,8 @@ def run_point(n: int, bench_args: List[str], timeout: float = 1800.0) -> Dict:
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)  # the child self-launches its own ranks
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + bench_args
+    # --full: the N = 1 point runs the replica check too (the curve's replica_ok column)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full"] + bench_args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     if r.returncode != 0 or not lines:
@@ -53,7 +54,7 @@ def curve(results: List[Dict]) -> Dict:
         out.append({"n_gpus": d["n_gpus"], "value": d["value"], "per_gpu": round(per, 2),
                     "ms_per_step": d["ms_per_step"],
                     "efficiency": round(per / base_per, 4) if base_per > 0 else None,
-                    "replica_ok": d.get("extra", {}).get("replica_check", {}).get("ok")})
+                    "replica_ok": (d.get("extra", {}).get("replica_check") or {}).get("ok")})
     return {"metric": base["metric"], "unit": base.get("unit"), "scaling": base.get("scaling"),
             "model": base["config"]["model"], "per_gpu_batch": base["config"].get("per_gpu_batch"),
             "dtype": base.get("dtype"), "data": base.get("data"), "base_n": base["n_gpus"],

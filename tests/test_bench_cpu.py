@@ -79,6 +79,39 @@ def test_bench_replica_check_catches_drift():
     assert res["extra"]["replica_check"]["max_rel_dev"] > 1e-3
 
 
+def test_bench_plain_vs_full_and_dump_outputs(tmp_path):
+    """A plain one-rank run stops at the headline (no replica check, no extras); ``--full``
+    adds the check.  ``--dump-outputs`` writes the last timed step's outputs as float arrays,
+    identical from run to run for the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for name, more in (("plain", []), ("full", ["--full"])):
+        d = tmp_path / name
+        r = _run_bench(["--cpu", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(d)] + more)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] > 0
+        assert res["value"] == pytest.approx(
+            res["config"]["global_batch"] / res["ms_per_step"] * 1e3, rel=1e-3)
+        rc = res["extra"]["replica_check"]
+        assert (rc is None) if name == "plain" else (rc["ok"] and len(rc["digests"]) == 1)
+        assert "edge" not in res["extra"] and "yolov8n" not in res["extra"]  # GPU-only extras
+        assert sorted(p.name for p in d.iterdir()) == ["probs.npy", "top1.npy"]
+        dumps.append({p.name: np.load(p) for p in d.iterdir()})
+    a, b = dumps
+    n = json.loads(lines[0])["config"]["per_gpu_batch"]
+    assert a["probs.npy"].dtype == np.float32 and a["probs.npy"].shape == (n, 1000)
+    assert a["top1.npy"].dtype in (np.float32, np.float64) and a["top1.npy"].shape == (n,)
+    assert np.allclose(a["probs.npy"].sum(1), 1.0, atol=1e-3)
+    assert (a["probs.npy"].argmax(1) == a["top1.npy"]).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_rejects_bad_gpus():
     r = _run_bench(["--cpu", "--gpus", "0"], timeout=300)
     assert r.returncode == 2 and "--gpus must be" in r.stderr

@@ -8,10 +8,10 @@ import pytest
 from kvedge_amd.utils import asciicast
 from kvedge_amd.utils.boottime import BootTimeline, parse_k8s_time, parse_stamps
 
-CAST = "/root/reference/deployment/az-iot-edge-k8s-kubevirt-ascii.cast"
+CAST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                    "az-iot-edge-k8s-kubevirt-ascii.cast")
 
 
-@pytest.mark.skipif(not os.path.exists(CAST), reason="reference recording not mounted")
 def test_reference_cast_reproduces_baseline_md():
     tl = asciicast.deployment_timeline(asciicast.load(CAST))
     m = tl.metrics()

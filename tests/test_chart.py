@@ -17,7 +17,6 @@ from kvedge_amd.deploy.helm import Chart, apply_sets, manifests
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHART = os.path.join(ROOT, "deploy", "helm")
-REF_CHART = "/root/reference/deployment/helm"
 A1 = {  # SURVEY.md Appendix A.1, nameOverride=aziot-edge-kubevirt
     ("Secret", "aziot-edge-kubevirt-vm-aziotedgeconfig"),
     ("Secret", "aziot-edge-kubevirt-vm-cloudconfig"),
@@ -45,16 +44,34 @@ def cfg_file(tmp_path):
     return str(p)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CHART), reason="reference chart not mounted")
-def test_renderer_on_reference_chart_matches_appendix_a1():
-    ch = Chart(REF_CHART)
-    out = ch.render("chart-1634218954", sets=["publicSshKey=k,aziotEdgeVmEnableExternalSsh=true"],
-                    set_strings=["azIotEdgeConfig=" + CFG])
+def test_renderer_typed_eq_on_minimal_chart(tmp_path):
+    """The renderer on a chart that guards a Service the way the reference's does
+    (``eq <value> true``): names come through a named template, a
+    bool true renders the Service, a STRING "true" does not."""
+    (tmp_path / "templates").mkdir()
+    (tmp_path / "Chart.yaml").write_text("apiVersion: v2\nname: mini\nversion: 0.1.0\n")
+    (tmp_path / "values.yaml").write_text(
+        "nameOverride: aziot-edge-kubevirt\nexternalSsh: false\npublicSshKey: ''\n")
+    (tmp_path / "templates" / "_names.tpl").write_text(
+        '{{- define "mini.name" -}}{{ default .Chart.Name .Values.nameOverride }}{{- end }}\n')
+    (tmp_path / "templates" / "secret.yaml").write_text(
+        'apiVersion: v1\nkind: Secret\nmetadata:\n  name: {{ include "mini.name" . }}-vm-cloudconfig\n'
+        'stringData:\n  key: {{ .Values.publicSshKey | quote }}\n')
+    (tmp_path / "templates" / "service.yaml").write_text(
+        '{{- if eq .Values.externalSsh true }}\napiVersion: v1\nkind: Service\nmetadata:\n'
+        '  name: {{ include "mini.name" . }}-vm-ssh-service\n{{- end }}\n')
+    (tmp_path / "templates" / "NOTES.txt").write_text(
+        'kubectl get vmi {{ include "mini.name" . }}-linux\n')
+    ch = Chart(str(tmp_path))
+    out = ch.render("chart-1634218954", sets=["publicSshKey=k,externalSsh=true"])
     objs = manifests(out)
-    assert {(o["kind"], o["metadata"]["name"]) for o in objs} == A1
-    # reference quirk A.2#7: a STRING "true" disables the reference's Service
-    out2 = ch.render("r", set_strings=["aziotEdgeVmEnableExternalSsh=true"])
+    assert {(o["kind"], o["metadata"]["name"]) for o in objs} == {
+        ("Secret", "aziot-edge-kubevirt-vm-cloudconfig"),
+        ("Service", "aziot-edge-kubevirt-vm-ssh-service")}
+    assert by_kind(objs, "Secret")[0]["stringData"]["key"] == "k"
+    out2 = ch.render("r", set_strings=["externalSsh=true"])
     assert not by_kind(manifests(out2), "Service")
+    assert by_kind(manifests(ch.render("r")), "Service") == []
     assert "kubectl get vmi aziot-edge-kubevirt-linux" in out["NOTES.txt"]
 
 

@@ -375,6 +375,11 @@ def test_module_refuses_cpu_when_gpu_required(tmp_path, capsys, monkeypatch):
     with pytest.raises(GpuUnavailableError, match="refusing to serve on the CPU"):
         ModuleApp(FakeTransport({"model": "simulated-temperature"}), device="cpu", require_gpus=1)
     hb = tmp_path / "heartbeat"
+    import torch
+
+    # the VM whose GPU did not come back, also where the test host has one
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 0)
     monkeypatch.setenv("KVEDGE_REQUIRE_GPU", "1")
     rc = entry.main(["--transport", "fake", "--model", "simulated-temperature", "--steps", "1",
                      "--heartbeat", str(hb), "--state", str(tmp_path / "s.json"),

@@ -157,7 +157,8 @@ def test_module_cli_topologies(tmp_path):
     import subprocess
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = dict(os.environ, PYTHONPATH=root, OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1")
+    base = dict(os.environ, PYTHONPATH=root, OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1",
+                CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")  # CPU ranks over gloo
     base.pop("WORLD_SIZE", None)
     # (a)
     env = dict(base, KVEDGE_NNODES="1", KVEDGE_RANKS_PER_NODE="2", KVEDGE_NODE_RANK="0",

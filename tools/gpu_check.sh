@@ -16,10 +16,10 @@ for s in $steps; do
     kernels) timeout -k 10 600 python -u -m pytest tests/test_kernels_gpu.py -x -q --timeout 120 \
              --timeout-method thread > "$out" 2>&1 ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out" 2>&1 ;;
-    bench) timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > "$out" 2>&1 ;;
+    bench) timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > "$out" 2>&1 ;;
     yolo) timeout -k 10 400 python -u bench.py --model yolov8n --steps 20 --warmup 5 --edge "" \
              > "$out" 2>&1 ;;
-    edge) timeout -k 10 400 python -u bench.py --steps 5 --warmup 2 --batch 64 > "$out" 2>&1 ;;
+    edge) timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 2 --batch 64 > "$out" 2>&1 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
   rc=$?
