@@ -624,6 +624,53 @@ void preprocess(const at::Tensor& x, at::Tensor& y, at::ArrayRef<double> mean,
   TORCH_CHECK(rc == 0, "kvedge: preprocess failed rc=", rc);
 }
 
+// K13: native-resolution frames -> model-size frames (csrc/kernels/frame_resize.hip); each
+// axis is {S, R, off, c0, cn} (kvedge_amd.ops.ResizePlan)
+void frame_resize(const at::Tensor& src, at::Tensor& dst, at::IntArrayRef axis_y,
+                  at::IntArrayRef axis_x, int64_t pad) {
+  check_dev(src, "src");
+  check_dev(dst, "dst");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 4 && src.size(3) == 3,
+              "kvedge: src u8 [N,Hs,Ws,3]");
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.dim() == 4 && dst.size(3) == 3 &&
+                  dst.size(0) == src.size(0), "kvedge: dst u8 [N,Hd,Wd,3]");
+  TORCH_CHECK(axis_y.size() == 5 && axis_x.size() == 5, "kvedge: axis_y / axis_x of 5 ints");
+  TORCH_CHECK(src.size(1) <= 8192 && src.size(2) <= 8192 && dst.size(1) <= 8192 &&
+                  dst.size(2) <= 8192, "kvedge: frame_resize extents are 1..8192");
+  TORCH_CHECK(src.device() == dst.device(), "kvedge: src / dst on different devices");
+  int ay[5], ax[5];
+  for (int i = 0; i < 5; ++i) {
+    TORCH_CHECK(axis_y[i] >= 0 && axis_y[i] <= 8192 && axis_x[i] >= 0 && axis_x[i] <= 8192,
+                "kvedge: frame_resize axis values are 0..8192");
+    ay[i] = (int)axis_y[i];
+    ax[i] = (int)axis_x[i];
+  }
+  const c10::DeviceGuard g(src.device());
+  const int rc = kv_frame_resize(src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(), (int)src.size(0),
+                                 (int)src.size(1), (int)src.size(2), (int)dst.size(1),
+                                 (int)dst.size(2), ay, ax, (int)pad, cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: frame_resize failed rc=", rc);
+}
+
+// K14: kept boxes back to source-frame pixels, in place; map = {cy, sy, cx, sx}
+void det_to_source(at::Tensor& det, const at::Tensor& count, at::ArrayRef<double> map, int64_t Hs,
+                   int64_t Ws) {
+  check_dev(det, "det");
+  check_dev(count, "count");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6,
+              "kvedge: det fp32 [N,max_det,6]");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == det.size(0),
+              "kvedge: count int32 [N]");
+  TORCH_CHECK(map.size() == 4, "kvedge: map = {cy, sy, cx, sx}");
+  TORCH_CHECK(Hs >= 1 && Ws >= 1 && Hs <= 8192 && Ws <= 8192, "kvedge: source size 1..8192");
+  TORCH_CHECK(det.device() == count.device(), "kvedge: det / count on different devices");
+  const c10::DeviceGuard g(det.device());
+  const int rc = kv_det_to_source(det.data_ptr<float>(), count.data_ptr<int>(), (int)det.size(0),
+                                  (int)det.size(1), (float)map[0], (float)map[1], (float)map[2],
+                                  (float)map[3], (int)Hs, (int)Ws, cur_stream(det));
+  TORCH_CHECK(rc == 0, "kvedge: det_to_source failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -737,6 +784,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("stem12_pool_frames(Tensor x, Tensor w, Tensor bias, Tensor(a!) y, float[] mean, float[] std, int y_coff) -> ()");
   m.def("yolo_stem2(Tensor x, Tensor w0, Tensor b0, Tensor w1, Tensor b1, Tensor(a!) y) -> ()");
   m.def("preprocess(Tensor x, Tensor(a!) y, float[] mean, float[] std) -> ()");
+  m.def("frame_resize(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
+  m.def("det_to_source(Tensor(a!) det, Tensor count, float[] map, int Hs, int Ws) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -774,6 +823,8 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("stem_pool_frames", stem_pool_frames);
   m.impl("stem12_pool_frames", stem12_pool_frames);
   m.impl("yolo_stem2", yolo_stem2);
+  m.impl("frame_resize", frame_resize);
+  m.impl("det_to_source", det_to_source);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

@@ -149,6 +149,20 @@ int kv_preprocess(const uint8_t* x, void* y, int N, int H, int W, const float* m
 //   (channel (dy*2+dx)*4 + c, c == 3 zero) for the stride-1 s2d stem conv.
 int kv_preprocess_s2d(const uint8_t* x, void* y, int N, int H, int W, const float* mean3,
                       const float* inv_std3, hipStream_t s);
+// K13 (frame_resize.hip): native-resolution uint8 frames [N,Hs,Ws,3] -> model-size uint8
+// frames [N,Hd,Wd,3], bilinear with half-pixel centres in 11-bit fixed point (bit-identical
+// to ops.reference.frame_resize).  Each axis is five ints {S, R, off, c0, cn}: source extent,
+// extent of the virtual resized image, crop offset inside it, first destination index that
+// holds content, number of content indices.  Destination pixels outside the content are
+// `pad` in all three channels; every destination byte is written.  Wd % 4 == 0, extents in
+// 1..8192.
+int kv_frame_resize(const uint8_t* src, uint8_t* dst, int N, int Hs, int Ws, int Hd, int Wd,
+                    const int* axis_y, const int* axis_x, int pad, hipStream_t s);
+// K14: kept boxes det fp32 [N,max_det,6] (x1,y1,x2,y2,score,cls; rows < count[n] only) from
+// model coordinates back to source-frame pixels, in place:
+// x = clamp((x - cx) * sx, 0, Ws), y = clamp((y - cy) * sy, 0, Hs).
+int kv_det_to_source(float* det, const int* count, int N, int max_det, float cy, float sy,
+                     float cx, float sx, int Hs, int Ws, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

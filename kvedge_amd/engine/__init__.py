@@ -14,7 +14,7 @@ from __future__ import annotations
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
@@ -71,11 +71,16 @@ class InferenceEngine:
     streams: split each step's batch into this many equal slices, each run by the model on
     its own HIP stream (forked from and joined back into the step's stream, so one hipGraph
     holds them as parallel branches); per-slice outputs are concatenated along the batch.
+    frame_hw: (Hs, Ws) of native-resolution input frames.  The input buffer is then
+    ``source_frames`` [B, Hs, Ws, 3]; every step resamples it into the model-size ``frames``
+    on the device by ``model.frame_plan`` (ops.frame_resize) before the model runs, and maps
+    the outputs back to the frame with ``model.to_source`` where the model has one -- all
+    inside the captured graph.  None: frames arrive at model size.
     """
 
     def __init__(self, model: Callable, batch: int, image_size: int, device="cuda",
                  seed: int = 0, use_graph: bool = True, synthetic: bool = True,
-                 streams: int = 1):
+                 streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None):
         self.model = model
         self.batch = batch
         self.hw = image_size
@@ -87,6 +92,19 @@ class InferenceEngine:
         self.synthetic = synthetic
         self.frames = torch.empty(batch, image_size, image_size, 3, dtype=torch.uint8,
                                   device=self.device)
+        # native-resolution input: self.frames becomes the resize destination
+        self.frame_hw = None
+        self.frame_plan = None
+        self.source_frames = None
+        if frame_hw is not None:
+            hs, ws = int(frame_hw[0]), int(frame_hw[1])
+            if synthetic and (batch * hs * ws * 3) % 8:
+                raise ValueError(f"synthetic {batch} x {hs}x{ws} frames: the generator writes "
+                                 f"8 bytes per thread and needs a byte count % 8 == 0")
+            self.frame_hw = (hs, ws)
+            self.frame_plan = model.frame_plan(self.frame_hw, image_size)
+            self.source_frames = torch.empty(batch, hs, ws, 3, dtype=torch.uint8,
+                                             device=self.device)
         # [step counter, finished-block count]: synth_frames bumps it in-kernel (one launch)
         self.step_ctr = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.outputs = None
@@ -102,15 +120,31 @@ class InferenceEngine:
         self._side = [torch.cuda.Stream(device=self.device, priority=-1 if (prio and i == 0) else 0)
                       for i in range(self.n_streams)] if self.n_streams > 1 else []
 
+    @property
+    def input_frames(self) -> torch.Tensor:
+        """The buffer frames are fed into (ring DMA, set_frames, the synthetic generator):
+        ``source_frames`` with a frame size configured, else the model-size ``frames``."""
+        return self.frames if self.source_frames is None else self.source_frames
+
     # one full edge-module step: synthesize frames, run the model
     def _step(self):
         if self.synthetic:
-            ops.synth_frames(self.frames, self.seed, self.step_ctr)
+            ops.synth_frames(self.input_frames, self.seed, self.step_ctr)
         return self._forward()
+
+    def _run_slice(self, lo: int, hi: int):
+        """Images [lo, hi) on the current stream: (resize ->) model (-> boxes to the frame)."""
+        frames = self.frames[lo:hi]
+        ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames)
+        out = self.model(frames)
+        if hasattr(self.model, "to_source"):
+            out = self.model.to_source(out, self.frame_plan)
+        return out
 
     def _forward(self):
         if not self._side:
-            self.outputs = self.model(self.frames)
+            self.outputs = (self.model(self.frames) if self.frame_plan is None
+                            else self._run_slice(0, self.batch))
             return self.outputs
         cur = torch.cuda.current_stream(self.device)
         per = self.batch // self.n_streams
@@ -118,7 +152,9 @@ class InferenceEngine:
         for i, s in enumerate(self._side):
             s.wait_stream(cur)
             with torch.cuda.stream(s):
-                parts.append(self.model(self.frames[i * per:(i + 1) * per]))
+                parts.append(self.model(self.frames[i * per:(i + 1) * per])
+                             if self.frame_plan is None
+                             else self._run_slice(i * per, (i + 1) * per))
         for s in self._side:
             cur.wait_stream(s)
         self.outputs = _cat_outputs(parts)
@@ -239,7 +275,7 @@ class InferenceEngine:
                      ring_timeout_ms: int = 1000):
         """Replay the captured step ``n_steps`` times from the native C++ loop
         (csrc/runtime: no Python per step, per-step device time into ``hist``).  With a
-        FrameRing, each step first DMAs one pinned frame batch into ``self.frames``
+        FrameRing, each step first DMAs one pinned frame batch into ``self.input_frames``
         (build the engine with synthetic=False so the graph does not overwrite them)."""
         from .. import runtime
 
@@ -249,7 +285,7 @@ class InferenceEngine:
             raise ValueError("ring-fed serving needs InferenceEngine(synthetic=False)")
         with torch.cuda.device(self.device):
             return runtime.serve(self.graph, n_steps, depth=depth, hist=hist, ring=ring,
-                                 dev_input=self.frames if ring is not None else None,
+                                 dev_input=self.input_frames if ring is not None else None,
                                  ring_timeout_ms=ring_timeout_ms)
 
     def memory_plan(self, align: int = 256):
@@ -260,7 +296,7 @@ class InferenceEngine:
 
     def set_frames(self, frames_u8: torch.Tensor):
         """Feed real frames instead of synthetic (disables the synthetic step)."""
-        self.frames.copy_(frames_u8)
+        self.input_frames.copy_(frames_u8)
         return self._forward()
 
 

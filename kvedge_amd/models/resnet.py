@@ -236,6 +236,12 @@ class KvResNet50:
             self._flops[hw] = count_flops(self._ref, (1, 3, hw, hw))
         return self._flops[hw]
 
+    def frame_plan(self, src_hw, image_size: int = 0) -> "ops.ResizePlan":
+        """Native-resolution frames [Hs, Ws] -> the model's square input: shorter side to
+        image_size * 8 / 7, then centre-crop (torchvision's 256 / 224).  ``image_size``: 0 =
+        the model's own."""
+        return ops.center_crop_plan(src_hw, image_size or self.image_size)
+
     def preprocess(self, frames_u8: torch.Tensor) -> torch.Tensor:
         return ops.preprocess(frames_u8, s2d=True)
 

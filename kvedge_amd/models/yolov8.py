@@ -395,6 +395,18 @@ class KvYoloV8n:
             self._flops[hw] = count_flops(self._ref, (1, 3, hw, hw))
         return self._flops[hw]
 
+    def frame_plan(self, src_hw, image_size: int = 0) -> "ops.ResizePlan":
+        """Native-resolution frames [Hs, Ws] -> the model's square input: letterbox (pad 114,
+        the Ultralytics convention).  ``image_size``: 0 = the model's own."""
+        return ops.letterbox_plan(src_hw, image_size or self.image_size)
+
+    def to_source(self, outputs, plan: "ops.ResizePlan"):
+        """(det, count) in model coordinates -> the same tensors with the kept boxes in
+        source-frame pixels (in place, ops.det_to_source)."""
+        det, count = outputs
+        ops.det_to_source(det, count, plan)
+        return det, count
+
     def preprocess(self, frames_u8: torch.Tensor) -> torch.Tensor:
         return ops.preprocess(frames_u8, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), s2d=True)
 

@@ -74,6 +74,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=d.seed)
     ap.add_argument("--report-interval-s", type=float, default=d.report_interval_s)
     ap.add_argument("--image-size", type=int, default=d.image_size)
+    ap.add_argument("--frame-height", type=int, default=d.frame_height,
+                    help="native frame height, resampled to the model size on the device "
+                         "(0 with --frame-width 0 = frames arrive at model size)")
+    ap.add_argument("--frame-width", type=int, default=d.frame_width,
+                    help="native frame width (a multiple of 8)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source, choices=["synthetic", "camera"])
@@ -103,7 +108,8 @@ def main(argv=None):
                        fps=a.fps, use_graph=not a.no_graph, world_size=di.world_size,
                        source=a.source, native_loop=not a.no_native_loop,
                        steps_per_poll=a.steps_per_poll, sync_every=a.sync_every,
-                       refine_s=a.refine_s).validate()
+                       refine_s=a.refine_s, frame_height=a.frame_height,
+                       frame_width=a.frame_width).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -114,11 +114,12 @@ class _CameraSource:
     thread; the hand-off path (pinned ring -> DMA in the native serve loop) is the
     production one."""
 
-    def __init__(self, ring, batch: int, hw: int, fps: float, seed: int):
+    def __init__(self, ring, batch: int, hw, fps: float, seed: int):
         import threading
 
+        h, w = (hw, hw) if isinstance(hw, int) else hw  # square model size, or (height, width)
         g = torch.Generator().manual_seed(seed)
-        self.frames = [torch.randint(0, 256, (batch, hw, hw, 3), dtype=torch.uint8, generator=g)
+        self.frames = [torch.randint(0, 256, (batch, h, w, 3), dtype=torch.uint8, generator=g)
                        for _ in range(3)]
         self.ring, self.batch, self.fps = ring, batch, fps
         self.seq = 0
@@ -413,7 +414,8 @@ class ModuleApp:
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
                                       seed=cfg.seed + self.rank, use_graph=cfg.use_graph,
                                       synthetic=not camera,
-                                      streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1)
+                                      streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1,
+                                      frame_hw=cfg.frame_hw())
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
@@ -435,8 +437,10 @@ class ModuleApp:
         if camera:
             from ..runtime import FrameRing
 
-            self.ring = FrameRing(3, self.engine.frames.numel())
-            self.camera = _CameraSource(self.ring, cfg.batch, cfg.resolved_image_size(), cfg.fps,
+            # one slot = one batch at the size frames arrive in (native, or model size)
+            self.ring = FrameRing(3, self.engine.input_frames.numel())
+            self.camera = _CameraSource(self.ring, cfg.batch,
+                                        cfg.frame_hw() or cfg.resolved_image_size(), cfg.fps,
                                         cfg.seed + self.rank)
 
     def _build_fleet(self, previous: Optional[ModuleConfig] = None) -> Optional[str]:
@@ -508,7 +512,8 @@ class ModuleApp:
             if self.ring is not None:  # host path: take one ring batch, feed it, release
                 slot, _ = self.ring.acquire_read(1000)
                 if slot >= 0:
-                    self.engine.frames.copy_(self.ring.slot(slot).view(self.engine.frames.shape))
+                    dst = self.engine.input_frames
+                    dst.copy_(self.ring.slot(slot).view(dst.shape))
                     self.ring.release(slot)
             self.engine.run()
             if self.device.type == "cuda":

@@ -33,7 +33,12 @@ class ModuleConfig:
     # frame source: "synthetic" = on-device generator inside the graph; "camera" = a host
     # producer thread feeding a pinned FrameRing that the native serve loop DMAs from
     source: str = "synthetic"
-    native_loop: bool = True     # GPU: replay the graph from the C++ serve loop
+    # native resolution of the incoming frames (e.g. 1080 x 1920); the engine resamples them
+    # to the model size on the device (YOLO: letterbox, ResNet: resize + centre-crop) and
+    # YOLO boxes are reported in frame pixels.  0 / 0 = frames arrive at model size
+    frame_height: int = 0
+    frame_width: int = 0
+    native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
     # 0 = off, the default).  It times runner-up tiles inside the captured step; on the
@@ -51,7 +56,7 @@ class ModuleConfig:
 
     # keys that force an engine rebuild when they change
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
-               "use_graph", "source")
+               "use_graph", "source", "frame_height", "frame_width")
 
     def validate(self) -> "ModuleConfig":
         if self.model not in MODELS:
@@ -72,6 +77,13 @@ class ModuleConfig:
             raise ValueError("max_det must be 1..300")
         if self.source not in SOURCES:
             raise ValueError(f"source must be one of {SOURCES}, got {self.source!r}")
+        if bool(self.frame_height) != bool(self.frame_width):
+            raise ValueError("frame_height and frame_width must be set together (0/0 = model size)")
+        if self.frame_height:
+            if not (16 <= self.frame_height <= 4096 and 16 <= self.frame_width <= 4096):
+                raise ValueError("frame_height / frame_width must be 16..4096")
+            if self.frame_width % 8:
+                raise ValueError("frame_width must be a multiple of 8")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -107,6 +119,10 @@ class ModuleConfig:
         if self.image_size:
             return self.image_size
         return 640 if self.model == "yolov8n" else 224
+
+    def frame_hw(self):
+        """(frame_height, frame_width), or None when frames arrive at model size."""
+        return (self.frame_height, self.frame_width) if self.frame_height else None
 
     def to_dict(self) -> Dict[str, Any]:
         return asdict(self)

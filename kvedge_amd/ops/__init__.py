@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -707,6 +707,103 @@ def preprocess(x: torch.Tensor, out: Optional[torch.Tensor] = None, mean=IMAGENE
     else:
         _ref.preprocess(x, out, mean, std)
     return out
+
+
+# ---------------------------------------------------------------------------
+# camera front end: native-resolution frames -> model-size frames, boxes back to the frame
+# ---------------------------------------------------------------------------
+RESIZE_MAX_EXTENT = 8192  # S, R <= 8192 keeps the fixed-point resample inside int32
+LETTERBOX_PAD = 114       # Ultralytics' letterbox grey
+
+
+@dataclass(frozen=True)
+class ResizePlan:
+    """Geometry of one frame resample (:func:`frame_resize`).  Each axis is five integers
+    ``(S, R, off, c0, cn)``: source extent, extent of the virtual resized image, offset of the
+    destination content origin inside it (the crop offset; 0 for letterbox), first
+    destination index holding content, number of destination indices holding content.
+    Destination pixels outside the content are ``pad``."""
+    axis_y: Tuple[int, int, int, int, int]
+    axis_x: Tuple[int, int, int, int, int]
+    pad: int
+    src_hw: Tuple[int, int]
+    dst_hw: Tuple[int, int]
+
+    def box_map(self) -> Tuple[float, float, float, float]:
+        """(cy, sy, cx, sx) of :func:`det_to_source`: source = (model - c) * s."""
+        (sy_, ry, oy, c0y, _), (sx_, rx, ox, c0x, _) = self.axis_y, self.axis_x
+        return float(c0y - oy), float(sy_ / ry), float(c0x - ox), float(sx_ / rx)
+
+
+def _check_src_hw(src_hw, dst: int) -> Tuple[int, int]:
+    hs, ws = int(src_hw[0]), int(src_hw[1])
+    if not (1 <= hs <= RESIZE_MAX_EXTENT and 1 <= ws <= RESIZE_MAX_EXTENT):
+        raise ValueError(f"frame size {hs}x{ws} outside 1..{RESIZE_MAX_EXTENT}")
+    if not 1 <= dst <= RESIZE_MAX_EXTENT:
+        raise ValueError(f"model size {dst} outside 1..{RESIZE_MAX_EXTENT}")
+    return hs, ws
+
+
+def letterbox_plan(src_hw, dst: int) -> ResizePlan:
+    """Ultralytics letterbox into ``dst`` x ``dst``: scale by min(dst/Hs, dst/Ws) (upscaling
+    allowed), centre, pad with 114."""
+    hs, ws = _check_src_hw(src_hw, dst)
+    r = min(dst / hs, dst / ws)
+    nw = min(dst, max(1, int(round(ws * r))))
+    nh = min(dst, max(1, int(round(hs * r))))
+    left = int(round((dst - nw) / 2 - 0.1))
+    top = int(round((dst - nh) / 2 - 0.1))
+    return ResizePlan((hs, nh, 0, top, nh), (ws, nw, 0, left, nw), LETTERBOX_PAD, (hs, ws),
+                      (dst, dst))
+
+
+def center_crop_plan(src_hw, dst: int) -> ResizePlan:
+    """torchvision's 256/224 convention: resize the shorter side to ``dst * 8 // 7`` (the
+    longer one in proportion, truncated), then centre-crop ``dst`` x ``dst``."""
+    hs, ws = _check_src_hw(src_hw, dst)
+    short = dst * 8 // 7
+    if hs <= ws:
+        rh, rw = short, int(short * ws / hs)
+    else:
+        rh, rw = int(short * hs / ws), short
+    if max(rh, rw) > RESIZE_MAX_EXTENT:
+        raise ValueError(f"resized frame {rh}x{rw} exceeds {RESIZE_MAX_EXTENT}")
+    oy, ox = int(round((rh - dst) / 2)), int(round((rw - dst) / 2))
+    return ResizePlan((hs, rh, oy, 0, dst), (ws, rw, ox, 0, dst), 0, (hs, ws), (dst, dst))
+
+
+def frame_resize(src: torch.Tensor, plan: ResizePlan,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames [N, Hs, Ws, 3] -> [N, Hd, Wd, 3] by ``plan``: bilinear, half-pixel
+    centres, no antialias (OpenCV INTER_LINEAR sampling), 11-bit fixed point; every byte of
+    ``out`` is written.  GPU (csrc/kernels/frame_resize.hip) and CPU reference are
+    bit-identical.  Wd % 4 == 0."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+    assert tuple(src.shape[1:3]) == tuple(plan.src_hw), (src.shape, plan.src_hw)
+    hd, wd = plan.dst_hw
+    if wd % 4:
+        raise ValueError(f"frame_resize needs a destination width % 4 == 0, got {wd}")
+    if out is None:
+        out = torch.empty(src.shape[0], hd, wd, 3, dtype=torch.uint8, device=src.device)
+    assert out.shape == (src.shape[0], hd, wd, 3), (out.shape, plan.dst_hw)
+    if src.is_cuda:
+        _native().frame_resize(src, out, list(plan.axis_y), list(plan.axis_x), plan.pad)
+    else:
+        _ref.frame_resize(src, plan, out)
+    return out
+
+
+def det_to_source(det: torch.Tensor, count: torch.Tensor, plan: ResizePlan) -> torch.Tensor:
+    """Kept boxes of :func:`nms` (det fp32 [N, max_det, 6], rows < count[n]) from model
+    coordinates to source-frame pixels, in place: x = clamp((x - cx) * sx, 0, Ws),
+    y = clamp((y - cy) * sy, 0, Hs).  Score, class and the rows past count are untouched."""
+    cy, sy, cx, sx = plan.box_map()
+    hs, ws = plan.src_hw
+    if det.is_cuda:
+        _native().det_to_source(det, count, [cy, sy, cx, sx], hs, ws)
+    else:
+        _ref.det_to_source(det, count, (cy, sy, cx, sx), hs, ws)
+    return det
 
 
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):

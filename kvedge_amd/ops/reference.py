@@ -164,6 +164,56 @@ def preprocess(x, out, mean, std):
     return out
 
 
+def _resize_axis(axis, D):
+    """Per destination index of one axis (S, R, off, c0, cn): content mask, the two source
+    taps and the 11-bit weight of the second one -- the integer formulas of
+    csrc/kernels/frame_resize.hip, in int64."""
+    S, R, off, c0, cn = axis
+    d = torch.arange(D, dtype=torch.int64)
+    content = (d >= c0) & (d < c0 + cn)
+    v = d - c0 + off
+    num = (2 * v + 1) * S - R
+    q = torch.div(num, 2 * R, rounding_mode="floor")
+    r = num - q * (2 * R)
+    w = torch.div(r * 2048 + R, 2 * R, rounding_mode="floor")
+    w = torch.where((q < 0) | (q >= S - 1), torch.zeros_like(w), w)
+    q = q.clamp(0, S - 1)  # (also keeps the taps of padding indices in range)
+    return content, q, (q + 1).clamp(max=S - 1), w
+
+
+def frame_resize(src, plan, out):
+    """Fixed-point bilinear resample (half-pixel centres, no antialias) of uint8 frames
+    [N, Hs, Ws, 3] into out [N, Hd, Wd, 3]; padding pixels are plan.pad."""
+    Hd, Wd = plan.dst_hw
+    cy, y0, y1, wy = _resize_axis(plan.axis_y, Hd)
+    cx, x0, x1, wx = _resize_axis(plan.axis_x, Wd)
+    top_rows, bot_rows = src[:, y0], src[:, y1]          # [N, Hd, Ws, 3] uint8
+    a, b = top_rows[:, :, x0].long(), top_rows[:, :, x1].long()
+    c, d = bot_rows[:, :, x0].long(), bot_rows[:, :, x1].long()
+    wx = wx.view(1, 1, Wd, 1)
+    wy = wy.view(1, Hd, 1, 1)
+    top = a * (2048 - wx) + b * wx
+    bot = c * (2048 - wx) + d * wx
+    y = (top * (2048 - wy) + bot * wy + (1 << 21)) >> 22
+    content = (cy.view(Hd, 1) & cx.view(1, Wd)).view(1, Hd, Wd, 1)
+    out.copy_(torch.where(content, y, torch.full_like(y, plan.pad)).to(torch.uint8))
+    return out
+
+
+def det_to_source(det, count, box_map, Hs, Ws):
+    """In place on rows < count[n]: x = clamp((x - cx) * sx, 0, Ws), y likewise (fp32)."""
+    cy, sy, cx, sx = box_map
+    N, max_det, _ = det.shape
+    live = (torch.arange(max_det).view(1, max_det) < count.view(N, 1).long()).unsqueeze(-1)
+    sub = torch.tensor([cx, cy, cx, cy], dtype=torch.float32)
+    mul = torch.tensor([sx, sy, sx, sy], dtype=torch.float32)
+    hi = torch.tensor([Ws, Hs, Ws, Hs], dtype=torch.float32)
+    box = det[..., :4]
+    new = torch.minimum(((box - sub) * mul).clamp_min(0.0), hi)
+    det[..., :4] = torch.where(live, new, box)
+    return det
+
+
 def conv_dual2(x, x_coff, K1, x2, x2_coff, w, bias, act, stride2, up2, out, y_coff):
     K2 = w.shape[1] - K1
     a = x[..., x_coff:x_coff + K1].float()
