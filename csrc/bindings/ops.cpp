@@ -671,6 +671,47 @@ void det_to_source(at::Tensor& det, const at::Tensor& count, at::ArrayRef<double
   TORCH_CHECK(rc == 0, "kvedge: det_to_source failed rc=", rc);
 }
 
+// K15: top-K detection boxes -> fixed-size uint8 crops (csrc/kernels/roi_crop.hip); K and D
+// are dst's shape.  band: destination rows per workgroup, 0 = the built-in choice.
+void roi_crop_band(const at::Tensor& src, const at::Tensor& det, const at::Tensor& count,
+                   at::Tensor& dst, int64_t pad, int64_t band) {
+  check_dev(src, "src");
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(dst, "dst");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 4 && src.size(3) == 3,
+              "kvedge: src u8 [N,Hs,Ws,3]");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6 &&
+                  det.size(0) == src.size(0), "kvedge: det fp32 [N,max_det,6]");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 &&
+                  count.size(0) == src.size(0), "kvedge: count int32 [N]");
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.dim() == 4 && dst.size(3) == 3 &&
+                  dst.size(1) == dst.size(2), "kvedge: dst u8 [N*K,D,D,3]");
+  const int64_t N = src.size(0);
+  TORCH_CHECK(N ? dst.size(0) >= N && dst.size(0) % N == 0 : dst.size(0) == 0,
+              "kvedge: dst holds N*K crops, K >= 1");
+  const int64_t K = N ? dst.size(0) / N : 1;
+  TORCH_CHECK(K <= det.size(1), "kvedge: roi_crop K ", K, " > max_det ", det.size(1));
+  TORCH_CHECK(src.size(1) <= 8192 && src.size(2) <= 8192 && dst.size(1) <= 8192,
+              "kvedge: roi_crop extents are 1..8192");
+  TORCH_CHECK(N * det.size(1) < (1ll << 31) && dst.size(0) < (1ll << 31),
+              "kvedge: roi_crop batch too large");
+  TORCH_CHECK(src.device() == det.device() && src.device() == count.device() &&
+                  src.device() == dst.device(), "kvedge: roi_crop operands on different devices");
+  TORCH_CHECK(band >= 0 && band <= 32, "kvedge: roi_crop band is 0, 4, 8, 16 or 32");
+  const c10::DeviceGuard g(src.device());
+  const int rc = kv_roi_crop_band(src.data_ptr<uint8_t>(), det.data_ptr<float>(),
+                                  count.data_ptr<int>(), dst.data_ptr<uint8_t>(), (int)N,
+                                  (int)src.size(1), (int)src.size(2), (int)det.size(1), (int)K,
+                                  (int)dst.size(1), (int)pad, (int)band, cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: roi_crop failed rc=", rc);
+}
+
+void roi_crop(const at::Tensor& src, const at::Tensor& det, const at::Tensor& count,
+              at::Tensor& dst, int64_t pad) {
+  roi_crop_band(src, det, count, dst, pad, 0);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -786,6 +827,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("preprocess(Tensor x, Tensor(a!) y, float[] mean, float[] std) -> ()");
   m.def("frame_resize(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
   m.def("det_to_source(Tensor(a!) det, Tensor count, float[] map, int Hs, int Ws) -> ()");
+  m.def("roi_crop(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad) -> ()");
+  m.def("roi_crop_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -825,6 +868,8 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("yolo_stem2", yolo_stem2);
   m.impl("frame_resize", frame_resize);
   m.impl("det_to_source", det_to_source);
+  m.impl("roi_crop", roi_crop);
+  m.impl("roi_crop_band", roi_crop_band);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

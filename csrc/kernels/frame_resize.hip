@@ -19,45 +19,14 @@
 // every destination byte is written on every launch.
 #include "common.h"
 #include "kvedge_kernels.h"
+#include "resample.h"  // RsAxis, rs_tap
 
 namespace kvedge {
 namespace {
 
 constexpr int kRsBlock = 256;
 constexpr int kRsBand = 8;       // destination rows per workgroup step
-constexpr int kRsMaxExtent = 8192;
 constexpr unsigned kRsPadCol = 0xffffffffu;
-
-struct RsAxis {
-  int S, R, off, c0, cn;
-};
-
-// taps and weight of destination index d; w = -1: d is padding
-__device__ __forceinline__ void rs_tap(const RsAxis& a, int d, int& q0, int& q1, int& w) {
-  if (d < a.c0 || d >= a.c0 + a.cn) {
-    q0 = q1 = 0;
-    w = -1;
-    return;
-  }
-  const int v = d - a.c0 + a.off;
-  const int num = (2 * v + 1) * a.S - a.R;
-  const int den = 2 * a.R;
-  int q = num >= 0 ? num / den : -((den - 1 - num) / den);  // floor
-  const int r = num - q * den;
-  w = (r * 2048 + a.R) / den;
-  if (q < 0) {
-    q = 0;
-    w = 0;
-  }
-  if (q >= a.S - 1) {
-    q = a.S - 1;
-    w = 0;
-  }
-  q0 = q;
-  // a zero weight never reads its second tap (b * 0): an exact integer ratio such as
-  // 1080 -> 360 then touches one source line per destination line instead of two
-  q1 = w ? min(q + 1, a.S - 1) : q;
-}
 
 __global__ __launch_bounds__(kRsBlock) void frame_resize_kernel(
     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int Hs, int Ws, int Hd, int Wd,
@@ -144,22 +113,6 @@ bool rs_axis_ok(const int* a, int S, int D) {
   return a[0] == S && a[0] >= 1 && a[0] <= kRsMaxExtent && a[1] >= 1 && a[1] <= kRsMaxExtent &&
          a[2] >= 0 && a[3] >= 0 && a[4] >= 0 && a[3] + a[4] <= D && a[2] + a[4] <= a[1];
 }
-
-#ifdef KVEDGE_CHECKS
-// bounds-check build: operand extents against their HIP allocations (as kv_conv_check_extents)
-bool rs_in_alloc(const void* ptr, long long bytes) {
-  if (!ptr || bytes <= 0) return true;
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  const char* b = static_cast<const char*>(base);
-  const char* q = static_cast<const char*>(ptr);
-  return q >= b && q + bytes <= b + size;
-}
-#endif
 
 }  // namespace
 }  // namespace kvedge

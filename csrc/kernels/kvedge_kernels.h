@@ -163,6 +163,19 @@ int kv_frame_resize(const uint8_t* src, uint8_t* dst, int N, int Hs, int Ws, int
 // x = clamp((x - cx) * sx, 0, Ws), y = clamp((y - cy) * sy, 0, Hs).
 int kv_det_to_source(float* det, const int* count, int N, int max_det, float cy, float sy,
                      float cx, float sx, int Hs, int Ws, hipStream_t s);
+// K15 (roi_crop.hip): crop n * K + k of dst u8 [N*K,D,D,3] is the window of box row k of
+// det fp32 [N,max_det,6] (x1,y1,x2,y2,score,cls in src pixels) cut from src u8 [N,Hs,Ws,3] and
+// stretched to D x D with K13's fixed-point bilinear (bit-identical to
+// ops.reference.roi_crop).  The window is clamped on the device to >= 1 x 1 inside the frame
+// for any box, non-finite ones included; slots k >= min(max(count[n], 0), max_det) are `pad`;
+// every destination byte is written.  D % 4 == 0, 1 <= K <= max_det, extents in 1..8192.
+// Returns -1 D % 4, -2 extents, -3 K, -4 pad, -5 misaligned dst, -6 N or grid, -7 band.
+int kv_roi_crop(const uint8_t* src, const float* det, const int* count, uint8_t* dst, int N,
+                int Hs, int Ws, int max_det, int K, int D, int pad, hipStream_t s);
+// ... with `band` destination rows per workgroup (4, 8, 16 or 32; 0 = the built-in choice):
+// the probe's knob (tools/roi_crop_probe.py), same result for every band
+int kv_roi_crop_band(const uint8_t* src, const float* det, const int* count, uint8_t* dst, int N,
+                     int Hs, int Ws, int max_det, int K, int D, int pad, int band, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

@@ -133,9 +133,13 @@ class InferenceEngine:
         return self._forward()
 
     def _run_slice(self, lo: int, hi: int):
-        """Images [lo, hi) on the current stream: (resize ->) model (-> boxes to the frame)."""
+        """Images [lo, hi) on the current stream: (resize ->) model (-> boxes to the frame).
+        A model with ``from_source`` (the detect-classify cascade) also gets the native
+        frames, to cut its crops from them."""
         frames = self.frames[lo:hi]
         ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames)
+        if hasattr(self.model, "from_source"):
+            return self.model.from_source(self.source_frames[lo:hi], frames, self.frame_plan)
         out = self.model(frames)
         if hasattr(self.model, "to_source"):
             out = self.model.to_source(out, self.frame_plan)

@@ -79,6 +79,9 @@ def main(argv=None):
                          "(0 with --frame-width 0 = frames arrive at model size)")
     ap.add_argument("--frame-width", type=int, default=d.frame_width,
                     help="native frame width (a multiple of 8)")
+    ap.add_argument("--crops-per-image", type=int, default=d.crops_per_image,
+                    help="--model detect-classify: boxes per frame cut out and classified "
+                         "(1..16, <= max_det)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source, choices=["synthetic", "camera"])
@@ -109,7 +112,8 @@ def main(argv=None):
                        source=a.source, native_loop=not a.no_native_loop,
                        steps_per_poll=a.steps_per_poll, sync_every=a.sync_every,
                        refine_s=a.refine_s, frame_height=a.frame_height,
-                       frame_width=a.frame_width).validate()
+                       frame_width=a.frame_width,
+                       crops_per_image=a.crops_per_image).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -8,7 +8,8 @@ but the workload is ResNet-50 / YOLOv8n on the passed-through MI355X:
              file on the persistent disk (checkpoint/resume).
   step():    one engine step (synthetic frames -> model) ; every report_interval_s a
              telemetry message on output "telemetry": images/sec, p50/p99 batch latency,
-             cumulative images, top-1 histogram (ResNet) / detections (YOLO), heartbeat.
+             cumulative images, top-1 histogram (ResNet) / detections (YOLO) / detections
+             + crop classes (detect-classify), heartbeat.
              With world_size > 1 the throughput counters are all-reduced over RCCL (C2)
              and rank 0 reports the job total.
   twin patch: validated; engine rebuilt only if a REBUILD key changed; reported props
@@ -409,6 +410,12 @@ class ModuleApp:
 
             self.model = KvYoloV8n(init_yolov8n(cfg.seed, calibrate=dev.type == "cuda"), dev,
                                    conf=cfg.conf, iou=cfg.iou, max_det=cfg.max_det)
+            if cfg.model == "detect-classify":
+                from ..models.cascade import KvDetectClassify
+                from ..models.resnet import KvResNet50
+
+                clf = KvResNet50.build(seed=cfg.seed, device=dev, calibrate=dev.type == "cuda")
+                self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
         camera = cfg.source == "camera"
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -707,9 +714,16 @@ class ModuleApp:
             vals, counts = torch.unique(top1, return_counts=True)
             order = counts.argsort(descending=True)[:5]
             return {"top1": {str(int(vals[i])): int(counts[i]) for i in order}}
-        dets, cnt = out
-        cnt = cnt.to("cpu")
-        return {"detections": {"total": int(cnt.sum()), "max_per_image": int(cnt.max())}}
+        cnt = out[1].to("cpu")
+        res = {"detections": {"total": int(cnt.sum()), "max_per_image": int(cnt.max())}}
+        if self.cfg.model == "detect-classify":
+            cls = out[2].to("cpu")
+            cls = cls[cls >= 0]  # valid slots
+            vals, counts = torch.unique(cls, return_counts=True)
+            order = counts.argsort(descending=True)[:5]
+            res["crops"] = int(cls.numel())
+            res["crop_top1"] = {str(int(vals[i])): int(counts[i]) for i in order}
+        return res
 
     # ---------------------------------------------------------------- handlers
     # Handlers run on the module thread from transport.poll(); they only queue work

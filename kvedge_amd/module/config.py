@@ -11,7 +11,7 @@ from __future__ import annotations
 from dataclasses import asdict, dataclass, fields, replace
 from typing import Any, Dict
 
-MODELS = ("resnet50", "yolov8n", "simulated-temperature")
+MODELS = ("resnet50", "yolov8n", "detect-classify", "simulated-temperature")
 SOURCES = ("synthetic", "camera")
 DTYPES = ("bf16",)
 
@@ -38,6 +38,10 @@ class ModuleConfig:
     # YOLO boxes are reported in frame pixels.  0 / 0 = frames arrive at model size
     frame_height: int = 0
     frame_width: int = 0
+    # model "detect-classify": the top crops_per_image boxes of every frame are cut out on the
+    # device and classified (ResNet-50 at 224); the classifier runs batch * crops_per_image
+    # images per step whatever the detection counts are
+    crops_per_image: int = 4
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -56,7 +60,7 @@ class ModuleConfig:
 
     # keys that force an engine rebuild when they change
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
-               "use_graph", "source", "frame_height", "frame_width")
+               "use_graph", "source", "frame_height", "frame_width", "crops_per_image")
 
     def validate(self) -> "ModuleConfig":
         if self.model not in MODELS:
@@ -84,6 +88,13 @@ class ModuleConfig:
                 raise ValueError("frame_height / frame_width must be 16..4096")
             if self.frame_width % 8:
                 raise ValueError("frame_width must be a multiple of 8")
+        if not 1 <= self.crops_per_image <= 16:
+            raise ValueError("crops_per_image must be 1..16")
+        if self.model == "detect-classify":  # cross-key limits bind the cascade only
+            if self.crops_per_image > self.max_det:
+                raise ValueError("crops_per_image must be <= max_det")
+            if self.batch * self.crops_per_image > 4096:
+                raise ValueError("batch * crops_per_image must be <= 4096")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -118,7 +129,7 @@ class ModuleConfig:
     def resolved_image_size(self) -> int:
         if self.image_size:
             return self.image_size
-        return 640 if self.model == "yolov8n" else 224
+        return 640 if self.model in ("yolov8n", "detect-classify") else 224
 
     def frame_hw(self):
         """(frame_height, frame_width), or None when frames arrive at model size."""

@@ -806,6 +806,41 @@ def det_to_source(det: torch.Tensor, count: torch.Tensor, plan: ResizePlan) -> t
     return det
 
 
+def roi_crop(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, size: int,
+             pad: int = 0, out: Optional[torch.Tensor] = None, band: int = 0) -> torch.Tensor:
+    """The top ``k`` boxes of every image as ``size`` x ``size`` uint8 crops
+    [N * k, size, size, 3]: crop ``n * k + j`` is the window of box row ``j`` of ``det[n]``
+    (fp32 [N, max_det, 6], boxes in ``src`` pixels; :func:`nms` rows are ordered by score) cut
+    from ``src`` [N, Hs, Ws, 3] and stretched with :func:`frame_resize`'s fixed-point bilinear.
+    The window is clamped to the frame and is at least 1 x 1 for any box, non-finite ones
+    included; slots ``j >= count[n]`` are ``pad``; every byte of ``out`` is written.  GPU
+    (csrc/kernels/roi_crop.hip) and CPU reference are bit-identical.  ``size % 4 == 0``,
+    ``1 <= k <= max_det``.  ``band``: destination rows per workgroup (GPU, 0 = built-in)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+    n = src.shape[0]
+    if size % 4:
+        raise ValueError(f"roi_crop needs a crop size % 4 == 0, got {size}")
+    if not 1 <= size <= RESIZE_MAX_EXTENT:
+        raise ValueError(f"crop size {size} outside 1..{RESIZE_MAX_EXTENT}")
+    if det.dim() != 3 or det.shape[0] != n or det.shape[2] != 6:
+        raise ValueError(f"det must be [N, max_det, 6] for N = {n}, got {tuple(det.shape)}")
+    if not 1 <= k <= det.shape[1]:
+        raise ValueError(f"roi_crop needs 1 <= k <= max_det = {det.shape[1]}, got {k}")
+    if not 0 <= pad <= 255:
+        raise ValueError(f"pad {pad} outside 0..255")
+    if out is None:
+        out = empty(n * k, size, size, 3, dtype=torch.uint8, device=src.device)
+    assert out.shape == (n * k, size, size, 3), (out.shape, (n * k, size, size, 3))
+    if src.is_cuda:
+        if band:
+            _native().roi_crop_band(src, det, count, out, pad, band)
+        else:
+            _native().roi_crop(src, det, count, out, pad)
+    else:
+        _ref.roi_crop(src, det, count, k, size, pad, out)
+    return out
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -214,6 +214,41 @@ def det_to_source(det, count, box_map, Hs, Ws):
     return det
 
 
+def roi_windows(boxes, Hs, Ws):
+    """Float boxes [..., >= 4] (x1, y1, x2, y2) -> integer windows [..., 4] (x0, y0, w, h):
+    clamp in fp32 (NaN -> 0 first, as the kernel's fmaxf(NaN, 0)), floor / ceil, at least
+    1 x 1 and always inside the Hs x Ws frame."""
+    b = torch.nan_to_num(boxes[..., :4].float(), nan=0.0)
+    lim = torch.tensor([Ws, Hs, Ws, Hs], dtype=torch.float32)
+    b = torch.minimum(b.clamp_min(0.0), lim)
+    x0 = b[..., 0].floor().long().clamp(max=Ws - 1)
+    y0 = b[..., 1].floor().long().clamp(max=Hs - 1)
+    xe = torch.maximum(b[..., 2].ceil().long(), x0 + 1).clamp(max=Ws)
+    ye = torch.maximum(b[..., 3].ceil().long(), y0 + 1).clamp(max=Hs)
+    return torch.stack([x0, y0, xe - x0, ye - y0], dim=-1)
+
+
+def roi_crop(src, det, count, K, D, pad, out):
+    """Crop n * K + k of out [N*K, D, D, 3]: the window of box row k of det[n] cut from
+    src[n] and stretched to D x D by frame_resize; slots k >= count[n] are ``pad``."""
+    from . import ResizePlan
+
+    N, Hs, Ws, _ = src.shape
+    max_det = det.shape[1]
+    win = roi_windows(det, Hs, Ws)
+    for n in range(N):
+        valid = min(max(int(count[n]), 0), max_det)
+        for k in range(K):
+            crop = out[n * K + k:n * K + k + 1]
+            if k >= valid:
+                crop.fill_(pad)
+                continue
+            x0, y0, w, h = (int(v) for v in win[n, k])
+            plan = ResizePlan((h, D, 0, 0, D), (w, D, 0, 0, D), pad, (h, w), (D, D))
+            frame_resize(src[n:n + 1, y0:y0 + h, x0:x0 + w], plan, crop)
+    return out
+
+
 def conv_dual2(x, x_coff, K1, x2, x2_coff, w, bias, act, stride2, up2, out, y_coff):
     K2 = w.shape[1] - K1
     a = x[..., x_coff:x_coff + K1].float()
