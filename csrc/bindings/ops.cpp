@@ -712,6 +712,79 @@ void roi_crop(const at::Tensor& src, const at::Tensor& det, const at::Tensor& co
   roi_crop_band(src, det, count, dst, pad, 0);
 }
 
+// K16: K13 from NV12 frames (csrc/kernels/frame_nv12.hip); src u8 [N, Hs*3/2, Ws] with Hs the
+// plan's source extent axis_y[0]
+void frame_resize_nv12(const at::Tensor& src, at::Tensor& dst, at::IntArrayRef axis_y,
+                       at::IntArrayRef axis_x, int64_t pad) {
+  check_dev(src, "src");
+  check_dev(dst, "dst");
+  TORCH_CHECK(axis_y.size() == 5 && axis_x.size() == 5, "kvedge: axis_y / axis_x of 5 ints");
+  int ay[5], ax[5];
+  for (int i = 0; i < 5; ++i) {
+    TORCH_CHECK(axis_y[i] >= 0 && axis_y[i] <= 8192 && axis_x[i] >= 0 && axis_x[i] <= 8192,
+                "kvedge: frame_resize_nv12 axis values are 0..8192");
+    ay[i] = (int)axis_y[i];
+    ax[i] = (int)axis_x[i];
+  }
+  const int64_t Hs = axis_y[0];
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 3 && src.size(1) * 2 == Hs * 3,
+              "kvedge: src u8 [N,Hs*3/2,Ws] with Hs = axis_y[0] = ", Hs, ", Hs even");
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.dim() == 4 && dst.size(3) == 3 &&
+                  dst.size(0) == src.size(0), "kvedge: dst u8 [N,Hd,Wd,3]");
+  TORCH_CHECK(src.size(2) <= 8192 && dst.size(1) <= 8192 && dst.size(2) <= 8192,
+              "kvedge: frame_resize_nv12 extents are 1..8192");
+  TORCH_CHECK(src.device() == dst.device(), "kvedge: src / dst on different devices");
+  const c10::DeviceGuard g(src.device());
+  const int rc = kv_frame_resize_nv12(src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(),
+                                      (int)src.size(0), (int)Hs, (int)src.size(2),
+                                      (int)dst.size(1), (int)dst.size(2), ay, ax, (int)pad,
+                                      cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: frame_resize_nv12 failed rc=", rc);
+}
+
+// K17: K15 from NV12 frames (csrc/kernels/frame_nv12.hip); src u8 [N, Hs*3/2, Ws], Hs =
+// src.size(1) * 2 / 3
+void roi_crop_nv12_band(const at::Tensor& src, const at::Tensor& det, const at::Tensor& count,
+                        at::Tensor& dst, int64_t pad, int64_t band) {
+  check_dev(src, "src");
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(dst, "dst");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 3 && src.size(1) % 3 == 0,
+              "kvedge: src u8 [N,Hs*3/2,Ws], Hs even");
+  const int64_t Hs = src.size(1) / 3 * 2;
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6 &&
+                  det.size(0) == src.size(0), "kvedge: det fp32 [N,max_det,6]");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 &&
+                  count.size(0) == src.size(0), "kvedge: count int32 [N]");
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.dim() == 4 && dst.size(3) == 3 &&
+                  dst.size(1) == dst.size(2), "kvedge: dst u8 [N*K,D,D,3]");
+  const int64_t N = src.size(0);
+  TORCH_CHECK(N ? dst.size(0) >= N && dst.size(0) % N == 0 : dst.size(0) == 0,
+              "kvedge: dst holds N*K crops, K >= 1");
+  const int64_t K = N ? dst.size(0) / N : 1;
+  TORCH_CHECK(K <= det.size(1), "kvedge: roi_crop_nv12 K ", K, " > max_det ", det.size(1));
+  TORCH_CHECK(Hs <= 8192 && src.size(2) <= 8192 && dst.size(1) <= 8192,
+              "kvedge: roi_crop_nv12 extents are 1..8192");
+  TORCH_CHECK(N * det.size(1) < (1ll << 31) && dst.size(0) < (1ll << 31),
+              "kvedge: roi_crop_nv12 batch too large");
+  TORCH_CHECK(src.device() == det.device() && src.device() == count.device() &&
+                  src.device() == dst.device(),
+              "kvedge: roi_crop_nv12 operands on different devices");
+  TORCH_CHECK(band >= 0 && band <= 32, "kvedge: roi_crop_nv12 band is 0, 4, 8, 16 or 32");
+  const c10::DeviceGuard g(src.device());
+  const int rc = kv_roi_crop_nv12_band(src.data_ptr<uint8_t>(), det.data_ptr<float>(),
+                                       count.data_ptr<int>(), dst.data_ptr<uint8_t>(), (int)N,
+                                       (int)Hs, (int)src.size(2), (int)det.size(1), (int)K,
+                                       (int)dst.size(1), (int)pad, (int)band, cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: roi_crop_nv12 failed rc=", rc);
+}
+
+void roi_crop_nv12(const at::Tensor& src, const at::Tensor& det, const at::Tensor& count,
+                   at::Tensor& dst, int64_t pad) {
+  roi_crop_nv12_band(src, det, count, dst, pad, 0);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -829,6 +902,9 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("det_to_source(Tensor(a!) det, Tensor count, float[] map, int Hs, int Ws) -> ()");
   m.def("roi_crop(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad) -> ()");
   m.def("roi_crop_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
+  m.def("frame_resize_nv12(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
+  m.def("roi_crop_nv12(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad) -> ()");
+  m.def("roi_crop_nv12_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -870,6 +946,9 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("det_to_source", det_to_source);
   m.impl("roi_crop", roi_crop);
   m.impl("roi_crop_band", roi_crop_band);
+  m.impl("frame_resize_nv12", frame_resize_nv12);
+  m.impl("roi_crop_nv12", roi_crop_nv12);
+  m.impl("roi_crop_nv12_band", roi_crop_nv12_band);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

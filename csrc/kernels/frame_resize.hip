@@ -19,7 +19,7 @@
 // every destination byte is written on every launch.
 #include "common.h"
 #include "kvedge_kernels.h"
-#include "resample.h"  // RsAxis, rs_tap
+#include "resample.h"  // RsAxis, rs_tap, rs_axis_ok
 
 namespace kvedge {
 namespace {
@@ -107,11 +107,6 @@ __global__ __launch_bounds__(kRsBlock) void det_to_source_kernel(float* __restri
     p[0] = a;
     p[1] = b;
   }
-}
-
-bool rs_axis_ok(const int* a, int S, int D) {
-  return a[0] == S && a[0] >= 1 && a[0] <= kRsMaxExtent && a[1] >= 1 && a[1] <= kRsMaxExtent &&
-         a[2] >= 0 && a[3] >= 0 && a[4] >= 0 && a[3] + a[4] <= D && a[2] + a[4] <= a[1];
 }
 
 }  // namespace

@@ -176,6 +176,19 @@ int kv_roi_crop(const uint8_t* src, const float* det, const int* count, uint8_t*
 // the probe's knob (tools/roi_crop_probe.py), same result for every band
 int kv_roi_crop_band(const uint8_t* src, const float* det, const int* count, uint8_t* dst, int N,
                      int Hs, int Ws, int max_det, int K, int D, int pad, int band, hipStream_t s);
+// K16 / K17 (frame_nv12.hip): K13 and K15 reading NV12 frames, src u8 [N, Hs * 3 / 2, Ws]
+// (rows 0 .. Hs - 1 are Y; row Hs + (y >> 1), bytes x & ~1 and (x & ~1) + 1 are U and V of
+// pixel (y, x)).  Each source tap is converted to RGB (integer BT.601 limited range, nv12.h)
+// and the taps are blended as in K13, so the result equals K13 / K15 on the converted frame
+// byte for byte.  Everything else as K13 / K15; in addition Hs and Ws are even (-8) and src is
+// 2-byte aligned (-9).
+int kv_frame_resize_nv12(const uint8_t* src, uint8_t* dst, int N, int Hs, int Ws, int Hd, int Wd,
+                         const int* axis_y, const int* axis_x, int pad, hipStream_t s);
+int kv_roi_crop_nv12(const uint8_t* src, const float* det, const int* count, uint8_t* dst, int N,
+                     int Hs, int Ws, int max_det, int K, int D, int pad, hipStream_t s);
+int kv_roi_crop_nv12_band(const uint8_t* src, const float* det, const int* count, uint8_t* dst,
+                          int N, int Hs, int Ws, int max_det, int K, int D, int pad, int band,
+                          hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

@@ -1,6 +1,7 @@
-// Fixed-point bilinear resample shared by frame_resize.hip (K13) and roi_crop.hip (K15): one
-// axis description, its tap / weight formula, and the bounds-check build's allocation probe.
-// The formulas are documented at the top of frame_resize.hip; both kernels and the CPU
+// Fixed-point bilinear resample shared by frame_resize.hip (K13), roi_crop.hip (K15) and their
+// NV12 forms in frame_nv12.hip (K16 / K17): one axis description, its tap / weight formula, the
+// ROI window, the launchers' axis check and the bounds-check build's allocation probe.
+// The formulas are documented at the top of frame_resize.hip; all kernels and the CPU
 // reference (kvedge_amd/ops/reference.py _resize_axis) compute exactly these integers.
 #pragma once
 #include "common.h"
@@ -40,6 +41,24 @@ __device__ __forceinline__ void rs_tap(const RsAxis& a, int d, int& q0, int& q1,
   // a zero weight never reads its second tap (b * 0): an exact integer ratio such as
   // 1080 -> 360 then touches one source line per destination line instead of two
   q1 = w ? min(q + 1, a.S - 1) : q;
+}
+
+// integer window [x0, x0 + w) of one ROI axis from the float box edges (lo, hi) in a frame of S
+// (the geometry is documented at the top of roi_crop.hip)
+__device__ __forceinline__ void roi_window(float lo, float hi, int S, int& x0, int& w) {
+  const float fs = (float)S;
+  const float flo = fminf(fmaxf(lo, 0.f), fs);
+  const float fhi = fminf(fmaxf(hi, 0.f), fs);
+  x0 = min((int)floorf(flo), S - 1);
+  const int xe = min(max((int)ceilf(fhi), x0 + 1), S);
+  w = xe - x0;
+}
+
+// launcher side: one axis tuple {S, R, off, c0, cn} against its source extent S and
+// destination extent D
+inline bool rs_axis_ok(const int* a, int S, int D) {
+  return a[0] == S && a[0] >= 1 && a[0] <= kRsMaxExtent && a[1] >= 1 && a[1] <= kRsMaxExtent &&
+         a[2] >= 0 && a[3] >= 0 && a[4] >= 0 && a[3] + a[4] <= D && a[2] + a[4] <= a[1];
 }
 
 #ifdef KVEDGE_CHECKS

@@ -25,7 +25,7 @@
 // (D % 4 == 0 keeps every row 4-byte aligned).
 #include "common.h"
 #include "kvedge_kernels.h"
-#include "resample.h"  // RsAxis, rs_tap
+#include "resample.h"  // RsAxis, rs_tap, roi_window
 
 namespace kvedge {
 namespace {
@@ -36,16 +36,6 @@ constexpr int kRoiBlock = 256;
 // 0.096 / 0.103 / 0.117 ms for 4 / 8 / 16 / 32 rows, ~64 px windows 0.058-0.060 ms for all
 // four.  4 and 8 tie within the run's spread; 8 builds half as many tap tables.
 constexpr int kRoiBand = 8;
-
-// integer window [x0, x0 + w) of one axis from the float box edges (lo, hi) in a frame of S
-__device__ __forceinline__ void roi_window(float lo, float hi, int S, int& x0, int& w) {
-  const float fs = (float)S;
-  const float flo = fminf(fmaxf(lo, 0.f), fs);
-  const float fhi = fminf(fmaxf(hi, 0.f), fs);
-  x0 = min((int)floorf(flo), S - 1);
-  const int xe = min(max((int)ceilf(fhi), x0 + 1), S);
-  w = xe - x0;
-}
 
 template <int BAND>
 __global__ __launch_bounds__(kRoiBlock) void roi_crop_kernel(

@@ -76,11 +76,23 @@ class InferenceEngine:
     on the device by ``model.frame_plan`` (ops.frame_resize) before the model runs, and maps
     the outputs back to the frame with ``model.to_source`` where the model has one -- all
     inside the captured graph.  None: frames arrive at model size.
+    frame_format: "rgb" (packed RGB24), or "nv12": native frames arrive as cameras and video
+    decoders deliver them, ``source_frames`` is [B, Hs * 3 // 2, Ws] (half the bytes through
+    the ring and over PCIe) and the resample converts each source tap to RGB on the way
+    (ops.frame_resize(..., src_format="nv12")).  NV12 needs ``frame_hw``.
     """
 
     def __init__(self, model: Callable, batch: int, image_size: int, device="cuda",
                  seed: int = 0, use_graph: bool = True, synthetic: bool = True,
-                 streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None):
+                 streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None,
+                 frame_format: str = "rgb"):
+        if frame_format not in ops.SRC_FORMATS:
+            raise ValueError(f"frame_format must be one of {ops.SRC_FORMATS}, "
+                             f"got {frame_format!r}")
+        if frame_format == "nv12" and frame_hw is None:
+            raise ValueError("frame_format='nv12' needs the size of the incoming frames: for "
+                             "frames that arrive at model size pass the model size as frame_hw")
+        self.frame_format = frame_format
         self.model = model
         self.batch = batch
         self.hw = image_size
@@ -98,13 +110,17 @@ class InferenceEngine:
         self.source_frames = None
         if frame_hw is not None:
             hs, ws = int(frame_hw[0]), int(frame_hw[1])
-            if synthetic and (batch * hs * ws * 3) % 8:
+            nv12 = frame_format == "nv12"
+            if nv12 and (hs % 2 or ws % 2):
+                raise ValueError(f"NV12 needs an even frame height and width, got {hs}x{ws}")
+            nbytes = batch * hs * ws * 3 // 2 if nv12 else batch * hs * ws * 3
+            if synthetic and nbytes % 8:
                 raise ValueError(f"synthetic {batch} x {hs}x{ws} frames: the generator writes "
                                  f"8 bytes per thread and needs a byte count % 8 == 0")
             self.frame_hw = (hs, ws)
             self.frame_plan = model.frame_plan(self.frame_hw, image_size)
-            self.source_frames = torch.empty(batch, hs, ws, 3, dtype=torch.uint8,
-                                             device=self.device)
+            shape = (batch, hs * 3 // 2, ws) if nv12 else (batch, hs, ws, 3)
+            self.source_frames = torch.empty(*shape, dtype=torch.uint8, device=self.device)
         # [step counter, finished-block count]: synth_frames bumps it in-kernel (one launch)
         self.step_ctr = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.outputs = None
@@ -129,7 +145,12 @@ class InferenceEngine:
     # one full edge-module step: synthesize frames, run the model
     def _step(self):
         if self.synthetic:
-            ops.synth_frames(self.input_frames, self.seed, self.step_ctr)
+            buf = self.input_frames
+            if buf.dim() == 3:
+                # NV12 [B, Hs * 3 // 2, Ws]: random bytes; the generator fills flat memory and
+                # takes it as 3-byte pixels, [B, Hs // 2, Ws, 3] is the same bytes
+                buf = buf.view(buf.shape[0], buf.shape[1] // 3, buf.shape[2], 3)
+            ops.synth_frames(buf, self.seed, self.step_ctr)
         return self._forward()
 
     def _run_slice(self, lo: int, hi: int):
@@ -137,9 +158,13 @@ class InferenceEngine:
         A model with ``from_source`` (the detect-classify cascade) also gets the native
         frames, to cut its crops from them."""
         frames = self.frames[lo:hi]
-        ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames)
+        # the format keyword only where it is not the default: models and plans written
+        # before NV12 keep their call signatures
+        fmt = {} if self.frame_format == "rgb" else {"src_format": self.frame_format}
+        ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames, **fmt)
         if hasattr(self.model, "from_source"):
-            return self.model.from_source(self.source_frames[lo:hi], frames, self.frame_plan)
+            return self.model.from_source(self.source_frames[lo:hi], frames, self.frame_plan,
+                                          **fmt)
         out = self.model(frames)
         if hasattr(self.model, "to_source"):
             out = self.model.to_source(out, self.frame_plan)

@@ -21,7 +21,7 @@ _OPS = ("conv2d", "conv_dual", "conv_dual2", "conv_tail", "conv_pair", "c2f16", 
         "stem_pool_frames", "stem12_pool_frames", "stem_from_frames", "yolo_stem2", "maxpool2d",
         "sppf_pool", "global_avgpool", "pooled_fc", "softmax_rows", "upsample2x", "yolo_decode",
         "nms", "synth_frames", "preprocess", "batchnorm_nhwc", "frame_resize", "det_to_source",
-        "roi_crop")
+        "roi_crop", "frame_resize_nv12", "roi_crop_nv12")
 
 
 def _shape_of(out):

@@ -55,11 +55,14 @@ class KvDetectClassify:
         """The detector's letterbox; the crops are cut from the native frames."""
         return self.detector.frame_plan(src_hw, image_size)
 
-    def classify(self, src_u8: torch.Tensor, det: torch.Tensor, count: torch.Tensor):
+    def classify(self, src_u8: torch.Tensor, det: torch.Tensor, count: torch.Tensor,
+                 src_format: str = "rgb"):
         """Boxes ``det`` / ``count`` in ``src_u8`` pixels -> (crop_cls, crop_prob) [N, K].
-        Device ops only: no host sync, capturable."""
+        ``src_format="nv12"``: ``src_u8`` is NV12 [N, Hs * 3 // 2, Ws] and the crops are cut
+        from it directly.  Device ops only: no host sync, capturable."""
         n = src_u8.shape[0]
-        crops = ops.roi_crop(src_u8, det, count, self.k, self.crop_size, pad=CROP_PAD)
+        crops = ops.roi_crop(src_u8, det, count, self.k, self.crop_size, pad=CROP_PAD,
+                             src_format=src_format)
         probs, top1 = self.classifier(crops)
         top1 = top1.view(n, self.k)
         prob = probs.gather(1, top1.view(-1, 1)).view(n, self.k)
@@ -73,10 +76,10 @@ class KvDetectClassify:
         return det, count, crop_cls, crop_prob
 
     def from_source(self, source_frames: torch.Tensor, frames: torch.Tensor,
-                    plan: "ops.ResizePlan"):
+                    plan: "ops.ResizePlan", src_format: str = "rgb"):
         """Native-resolution serving (InferenceEngine(frame_hw=...)): detect on the resized
         ``frames``, map the kept boxes to frame pixels, cut the crops from ``source_frames``
-        at full resolution."""
+        at full resolution (``src_format="nv12"``: from the NV12 frames)."""
         det, count = self.detector.to_source(self.detector(frames), plan)
-        crop_cls, crop_prob = self.classify(source_frames, det, count)
+        crop_cls, crop_prob = self.classify(source_frames, det, count, src_format=src_format)
         return det, count, crop_cls, crop_prob

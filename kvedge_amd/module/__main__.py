@@ -84,7 +84,10 @@ def main(argv=None):
                          "(1..16, <= max_det)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--source", default=d.source, choices=["synthetic", "camera"])
+    ap.add_argument("--source", default=d.source,
+                    choices=["synthetic", "camera", "camera-nv12"],
+                    help="camera-nv12: NV12 frames through the ring (needs --frame-height / "
+                         "--frame-width)")
     ap.add_argument("--no-native-loop", action="store_true")
     ap.add_argument("--steps-per-poll", type=int, default=d.steps_per_poll)
     ap.add_argument("--refine-s", type=float, default=d.refine_s,

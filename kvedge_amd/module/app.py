@@ -109,18 +109,20 @@ class _SimTempModel:
 
 
 class _CameraSource:
-    """Host frame producer for source="camera": cycles a few pre-rendered uint8 batches
+    """Host frame producer for source="camera" / "camera-nv12": cycles a few pre-rendered
+    uint8 batches ([B, H, W, 3], or NV12 [B, H * 3 // 2, W])
     into a pinned FrameRing (drop-oldest when paced and the GPU falls behind), at ``fps``
     frames/s (0 = as fast as the ring drains).  Stands in for a camera / RTSP decoder
     thread; the hand-off path (pinned ring -> DMA in the native serve loop) is the
     production one."""
 
-    def __init__(self, ring, batch: int, hw, fps: float, seed: int):
+    def __init__(self, ring, batch: int, hw, fps: float, seed: int, nv12: bool = False):
         import threading
 
         h, w = (hw, hw) if isinstance(hw, int) else hw  # square model size, or (height, width)
         g = torch.Generator().manual_seed(seed)
-        self.frames = [torch.randint(0, 256, (batch, h, w, 3), dtype=torch.uint8, generator=g)
+        shape = (batch, h * 3 // 2, w) if nv12 else (batch, h, w, 3)
+        self.frames = [torch.randint(0, 256, shape, dtype=torch.uint8, generator=g)
                        for _ in range(3)]
         self.ring, self.batch, self.fps = ring, batch, fps
         self.seq = 0
@@ -416,13 +418,13 @@ class ModuleApp:
 
                 clf = KvResNet50.build(seed=cfg.seed, device=dev, calibrate=dev.type == "cuda")
                 self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
-        camera = cfg.source == "camera"
+        camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
                                       seed=cfg.seed + self.rank, use_graph=cfg.use_graph,
                                       synthetic=not camera,
                                       streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1,
-                                      frame_hw=cfg.frame_hw())
+                                      frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format())
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
@@ -448,7 +450,8 @@ class ModuleApp:
             self.ring = FrameRing(3, self.engine.input_frames.numel())
             self.camera = _CameraSource(self.ring, cfg.batch,
                                         cfg.frame_hw() or cfg.resolved_image_size(), cfg.fps,
-                                        cfg.seed + self.rank)
+                                        cfg.seed + self.rank,
+                                        nv12=cfg.frame_format() == "nv12")
 
     def _build_fleet(self, previous: Optional[ModuleConfig] = None) -> Optional[str]:
         """Build on every rank; if ANY rank failed (HBM exhausted, bad shape), every rank

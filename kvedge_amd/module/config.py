@@ -12,7 +12,7 @@ from dataclasses import asdict, dataclass, fields, replace
 from typing import Any, Dict
 
 MODELS = ("resnet50", "yolov8n", "detect-classify", "simulated-temperature")
-SOURCES = ("synthetic", "camera")
+SOURCES = ("synthetic", "camera", "camera-nv12")
 DTYPES = ("bf16",)
 
 
@@ -31,7 +31,11 @@ class ModuleConfig:
     fps: float = 0.0             # 0 = run flat out; > 0 throttles batches/s*batch
     use_graph: bool = True
     # frame source: "synthetic" = on-device generator inside the graph; "camera" = a host
-    # producer thread feeding a pinned FrameRing that the native serve loop DMAs from
+    # producer thread feeding a pinned FrameRing that the native serve loop DMAs from;
+    # "camera-nv12" = the same with NV12 frames [Hs * 3 / 2, Ws] as capture devices and video
+    # decoders deliver them (1.5 bytes per pixel through the ring and over PCIe instead of 3;
+    # the colour conversion happens inside the on-device resample).  It needs frame_height /
+    # frame_width (for model-size frames, set them to the model size)
     source: str = "synthetic"
     # native resolution of the incoming frames (e.g. 1080 x 1920); the engine resamples them
     # to the model size on the device (YOLO: letterbox, ResNet: resize + centre-crop) and
@@ -88,6 +92,12 @@ class ModuleConfig:
                 raise ValueError("frame_height / frame_width must be 16..4096")
             if self.frame_width % 8:
                 raise ValueError("frame_width must be a multiple of 8")
+        if self.source == "camera-nv12":
+            if not self.frame_height:
+                raise ValueError("source camera-nv12 needs frame_height and frame_width (for "
+                                 "frames at model size, set them to the model size)")
+            if self.frame_height % 2:
+                raise ValueError("source camera-nv12 needs an even frame_height")
         if not 1 <= self.crops_per_image <= 16:
             raise ValueError("crops_per_image must be 1..16")
         if self.model == "detect-classify":  # cross-key limits bind the cascade only
@@ -134,6 +144,14 @@ class ModuleConfig:
     def frame_hw(self):
         """(frame_height, frame_width), or None when frames arrive at model size."""
         return (self.frame_height, self.frame_width) if self.frame_height else None
+
+    def is_camera(self) -> bool:
+        """A host producer feeds the ring (any frame format)."""
+        return self.source in ("camera", "camera-nv12")
+
+    def frame_format(self) -> str:
+        """Format of the incoming frames (InferenceEngine frame_format)."""
+        return "nv12" if self.source == "camera-nv12" else "rgb"
 
     def to_dict(self) -> Dict[str, Any]:
         return asdict(self)

@@ -772,14 +772,58 @@ def center_crop_plan(src_hw, dst: int) -> ResizePlan:
     return ResizePlan((hs, rh, oy, 0, dst), (ws, rw, ox, 0, dst), 0, (hs, ws), (dst, dst))
 
 
-def frame_resize(src: torch.Tensor, plan: ResizePlan,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+SRC_FORMATS = ("rgb", "nv12")
+
+
+def _check_nv12(src: torch.Tensor, hs: Optional[int] = None) -> Tuple[int, int]:
+    """(Hs, Ws) of NV12 frames uint8 [N, Hs * 3 // 2, Ws]; ``hs``: the height they must have."""
+    if src.dtype != torch.uint8 or src.dim() != 3:
+        raise ValueError(f"NV12 frames are uint8 [N, Hs * 3 / 2, Ws], got {src.dtype} "
+                         f"{tuple(src.shape)}")
+    rows, ws = int(src.shape[1]), int(src.shape[2])
+    if hs is None:
+        hs = rows * 2 // 3
+    if hs % 2 or ws % 2:
+        raise ValueError(f"NV12 needs an even frame height and width, got {hs}x{ws}")
+    if rows != hs * 3 // 2:
+        raise ValueError(f"NV12 frames of height {hs} have {hs * 3 // 2} rows (Y plane + "
+                         f"half-height UV plane), got {rows}")
+    return hs, ws
+
+
+def _check_format(src_format: str) -> None:
+    if src_format not in SRC_FORMATS:
+        raise ValueError(f"src_format must be one of {SRC_FORMATS}, got {src_format!r}")
+
+
+def nv12_to_rgb(src: torch.Tensor) -> torch.Tensor:
+    """NV12 frames uint8 [N, Hs * 3 // 2, Ws] -> RGB uint8 [N, Hs, Ws, 3]: integer BT.601
+    limited range, nearest-neighbour chroma -- the conversion the NV12 kernels apply to every
+    source tap (csrc/kernels/nv12.h).  A host-side reference, not a device kernel: GPU
+    tensors are converted on the CPU and copied back (the serving path never materialises
+    the RGB frame; it reads NV12 through ``src_format="nv12"``)."""
+    _check_nv12(src)
+    return _ref.nv12_to_rgb(src.cpu()).to(src.device)
+
+
+def frame_resize(src: torch.Tensor, plan: ResizePlan, out: Optional[torch.Tensor] = None,
+                 src_format: str = "rgb") -> torch.Tensor:
     """uint8 frames [N, Hs, Ws, 3] -> [N, Hd, Wd, 3] by ``plan``: bilinear, half-pixel
     centres, no antialias (OpenCV INTER_LINEAR sampling), 11-bit fixed point; every byte of
     ``out`` is written.  GPU (csrc/kernels/frame_resize.hip) and CPU reference are
-    bit-identical.  Wd % 4 == 0."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
-    assert tuple(src.shape[1:3]) == tuple(plan.src_hw), (src.shape, plan.src_hw)
+    bit-identical.  Wd % 4 == 0.
+    ``src_format="nv12"``: ``src`` is NV12 [N, Hs * 3 // 2, Ws] (Hs, Ws even) and every source
+    tap is converted to RGB before the blend (csrc/kernels/frame_nv12.hip), so the result
+    equals ``frame_resize(nv12_to_rgb(src), plan)`` byte for byte -- which is how the CPU
+    path computes it."""
+    _check_format(src_format)
+    nv12 = src_format == "nv12"
+    if nv12:
+        hs, ws = _check_nv12(src, int(plan.src_hw[0]))
+        assert ws == plan.src_hw[1], (src.shape, plan.src_hw)
+    else:
+        assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+        assert tuple(src.shape[1:3]) == tuple(plan.src_hw), (src.shape, plan.src_hw)
     hd, wd = plan.dst_hw
     if wd % 4:
         raise ValueError(f"frame_resize needs a destination width % 4 == 0, got {wd}")
@@ -787,9 +831,10 @@ def frame_resize(src: torch.Tensor, plan: ResizePlan,
         out = torch.empty(src.shape[0], hd, wd, 3, dtype=torch.uint8, device=src.device)
     assert out.shape == (src.shape[0], hd, wd, 3), (out.shape, plan.dst_hw)
     if src.is_cuda:
-        _native().frame_resize(src, out, list(plan.axis_y), list(plan.axis_x), plan.pad)
+        op = _native().frame_resize_nv12 if nv12 else _native().frame_resize
+        op(src, out, list(plan.axis_y), list(plan.axis_x), plan.pad)
     else:
-        _ref.frame_resize(src, plan, out)
+        _ref.frame_resize(_ref.nv12_to_rgb(src) if nv12 else src, plan, out)
     return out
 
 
@@ -807,7 +852,8 @@ def det_to_source(det: torch.Tensor, count: torch.Tensor, plan: ResizePlan) -> t
 
 
 def roi_crop(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, size: int,
-             pad: int = 0, out: Optional[torch.Tensor] = None, band: int = 0) -> torch.Tensor:
+             pad: int = 0, out: Optional[torch.Tensor] = None, band: int = 0,
+             src_format: str = "rgb") -> torch.Tensor:
     """The top ``k`` boxes of every image as ``size`` x ``size`` uint8 crops
     [N * k, size, size, 3]: crop ``n * k + j`` is the window of box row ``j`` of ``det[n]``
     (fp32 [N, max_det, 6], boxes in ``src`` pixels; :func:`nms` rows are ordered by score) cut
@@ -815,8 +861,16 @@ def roi_crop(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, 
     The window is clamped to the frame and is at least 1 x 1 for any box, non-finite ones
     included; slots ``j >= count[n]`` are ``pad``; every byte of ``out`` is written.  GPU
     (csrc/kernels/roi_crop.hip) and CPU reference are bit-identical.  ``size % 4 == 0``,
-    ``1 <= k <= max_det``.  ``band``: destination rows per workgroup (GPU, 0 = built-in)."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+    ``1 <= k <= max_det``.  ``band``: destination rows per workgroup (GPU, 0 = built-in).
+    ``src_format="nv12"``: ``src`` is NV12 [N, Hs * 3 // 2, Ws] (Hs, Ws even; boxes in its
+    Hs x Ws pixels) and the result equals ``roi_crop(nv12_to_rgb(src), ...)`` byte for byte
+    (csrc/kernels/frame_nv12.hip; the CPU path computes exactly that composition)."""
+    _check_format(src_format)
+    nv12 = src_format == "nv12"
+    if nv12:
+        _check_nv12(src)
+    else:
+        assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
     n = src.shape[0]
     if size % 4:
         raise ValueError(f"roi_crop needs a crop size % 4 == 0, got {size}")
@@ -832,13 +886,27 @@ def roi_crop(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, 
         out = empty(n * k, size, size, 3, dtype=torch.uint8, device=src.device)
     assert out.shape == (n * k, size, size, 3), (out.shape, (n * k, size, size, 3))
     if src.is_cuda:
+        nat = _native()
         if band:
-            _native().roi_crop_band(src, det, count, out, pad, band)
+            (nat.roi_crop_nv12_band if nv12 else nat.roi_crop_band)(src, det, count, out, pad,
+                                                                     band)
         else:
-            _native().roi_crop(src, det, count, out, pad)
+            (nat.roi_crop_nv12 if nv12 else nat.roi_crop)(src, det, count, out, pad)
     else:
-        _ref.roi_crop(src, det, count, k, size, pad, out)
+        _ref.roi_crop(_ref.nv12_to_rgb(src) if nv12 else src, det, count, k, size, pad, out)
     return out
+
+
+def frame_resize_nv12(src: torch.Tensor, plan: ResizePlan,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`frame_resize` of NV12 frames [N, Hs * 3 // 2, Ws]."""
+    return frame_resize(src, plan, out=out, src_format="nv12")
+
+
+def roi_crop_nv12(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, size: int,
+                  pad: int = 0, out: Optional[torch.Tensor] = None, band: int = 0) -> torch.Tensor:
+    """:func:`roi_crop` from NV12 frames [N, Hs * 3 // 2, Ws]."""
+    return roi_crop(src, det, count, k, size, pad=pad, out=out, band=band, src_format="nv12")
 
 
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):

@@ -200,6 +200,24 @@ def frame_resize(src, plan, out):
     return out
 
 
+def nv12_to_rgb(src):
+    """NV12 frames uint8 [N, Hs * 3 // 2, Ws] (Hs, Ws even; rows 0 .. Hs - 1 are Y, row
+    Hs + (y >> 1) holds U at byte x & ~1 and V at (x & ~1) + 1 for pixel (y, x)) -> RGB uint8
+    [N, Hs, Ws, 3]: integer BT.601 limited range with nearest-neighbour chroma, the integers
+    of csrc/kernels/nv12.h (int32 arithmetic shift = floor)."""
+    N, rows, Ws = src.shape
+    Hs = rows * 2 // 3
+    if Hs % 2 or Ws % 2 or Hs * 3 // 2 != rows:
+        raise ValueError(f"NV12 frames are [N, Hs * 3 / 2, Ws] with even Hs and Ws, "
+                         f"got {tuple(src.shape)}")
+    c = 298 * (src[:, :Hs].to(torch.int32) - 16) + 128
+    uv = src[:, Hs:].reshape(N, Hs // 2, Ws // 2, 2).to(torch.int32) - 128
+    uv = uv.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)  # [N, Hs, Ws, 2]
+    d, e = uv[..., 0], uv[..., 1]
+    rgb = torch.stack([c + 409 * e, c - 100 * d - 208 * e, c + 516 * d], dim=-1) >> 8
+    return rgb.clamp_(0, 255).to(torch.uint8)
+
+
 def det_to_source(det, count, box_map, Hs, Ws):
     """In place on rows < count[n]: x = clamp((x - cx) * sx, 0, Ws), y likewise (fp32)."""
     cy, sy, cx, sx = box_map
