@@ -249,6 +249,12 @@ def conv2d(x: torch.Tensor, spec: ConvSpec, w: torch.Tensor, bias: Optional[torc
     assert out.shape[:3] == (N, Ho, Wo), (out.shape, (N, Ho, Wo))
     ldy = out.shape[3]
     ldr = res.shape[-1] if res is not None else 0
+    # in place (YOLO C2f: residual and output are slices of one concat buffer): the kernels'
+    # workgroups read residual channels while others write output channels, in no order
+    if (res is not None and res.data_ptr() == out.data_ptr() and ldr == ldy
+            and r_coff < y_coff + spec.cout and y_coff < r_coff + spec.cout):
+        raise ValueError(f"kvedge: residual slice [{r_coff}, {r_coff + spec.cout}) and output "
+                         f"slice [{y_coff}, {y_coff + spec.cout}) of one buffer overlap")
     if x.is_cuda:
         ws = splitk_workspace(x.device, N * Ho * Wo * spec.cout) if is_splitk(tile) else None
         _native().conv(x, w, bias, res, out, N, H, W, spec.cin_eff, ldx, x_coff, Ho, Wo,

@@ -7,6 +7,7 @@ the native library: tests assert it is loaded (no silent fallback).
 import pytest
 import torch
 
+import epilogue_cases
 from kvedge_amd import ops
 from kvedge_amd.ops import ConvSpec
 
@@ -148,7 +149,11 @@ def _de_takes(tile, cin, cout, k, s, act, res):
     instantiations (no slicing)."""
     if res:
         return (cin, cout, k, s, act) in DE_RES_SHAPES[tile - DE0]
-    shapes = DE_SHAPES[tile - DE0]
+    return _direct_covers(DE_SHAPES[tile - DE0], cin, cout, k, s, act)
+
+
+def _direct_covers(shapes, cin, cout, k, s, act):
+    """direct_launch() without a residual: an instantiated shape, or Cout slices of them."""
     if (cin, cout, k, s, act) in shapes:
         return True
     if cout % 16:
@@ -161,6 +166,36 @@ def _de_takes(tile, cin, cout, k, s, act, res):
             return False
         done += best
     return True
+
+
+# (cin, cout, k, stride, act) the v4 tiles 54-57 instantiate (conv_direct.hip kDirect, the
+# plain forms: a v4 tile falls back to any of them, whatever its own patch-fetch form)
+DIRECT_SHAPES = {
+    (64, 64, 3, 1, ops.ACT_RELU), (64, 64, 3, 1, ops.ACT_NONE), (16, 32, 3, 2, ops.ACT_SILU),
+    (16, 16, 3, 1, ops.ACT_SILU), (32, 64, 3, 2, ops.ACT_SILU), (32, 32, 3, 1, ops.ACT_SILU),
+    (64, 128, 3, 2, ops.ACT_SILU), (64, 64, 3, 1, ops.ACT_SILU), (64, 64, 3, 2, ops.ACT_SILU),
+    (64, 128, 3, 1, ops.ACT_SILU), (64, 16, 3, 1, ops.ACT_SILU), (80, 80, 3, 1, ops.ACT_SILU),
+    (128, 128, 3, 1, ops.ACT_RELU),
+    (32, 32, 1, 1, ops.ACT_SILU), (48, 32, 1, 1, ops.ACT_SILU), (64, 64, 1, 1, ops.ACT_SILU),
+    (128, 64, 1, 1, ops.ACT_SILU), (192, 64, 1, 1, ops.ACT_SILU), (96, 64, 1, 1, ops.ACT_SILU),
+    (64, 64, 1, 1, ops.ACT_NONE), (80, 80, 1, 1, ops.ACT_NONE)}
+# ... with a residual: only x + SiLU(conv), no Cout slicing
+DIRECT_RES_SHAPES = {(16, 16, 3, 1, ops.ACT_SILU), (32, 32, 3, 1, ops.ACT_SILU),
+                     (64, 64, 3, 1, ops.ACT_SILU)}
+
+
+def _direct_res_form(act_bits, res):
+    """direct_plan(): with a residual, v4 / v10 compute only act(conv) + res (or no act)."""
+    return not res or bool(act_bits & ops.RES_AFTER_ACT) or (act_bits & 3) == ops.ACT_NONE
+
+
+def _v4_takes(cin, cout, k, s, act_bits, res):
+    """Mirror of direct_plan() / direct_launch() for the v4 tiles (stride-1 same-size convs)."""
+    if not _direct_res_form(act_bits, res):
+        return False
+    if res:
+        return (cin, cout, k, s, act_bits & 3) in DIRECT_RES_SHAPES
+    return _direct_covers(DIRECT_SHAPES, cin, cout, k, s, act_bits & 3)
 NLOOP_KPAD = [128, 256, 256, 256, 256, 384, 384, 768, 256, 256]
 NLOOP_DUAL = {63, 64, 65}
 STREAM0 = 32  # v3 tiles take 1x1 stride-1 GEMMs and dual-source convs only
@@ -1033,3 +1068,174 @@ def test_conv_pp(tile, case):
     torch.cuda.synchronize()
     assert not torch.isnan(outs[0].float()).any()
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+
+
+# ---------------------------------------------------------------------------
+# Epilogue matrix: the autotuner pins whichever tile is fastest and never compares outputs,
+# so every tile that accepts a call must compute it -- residual read from a channel slice
+# (ldr != Cout, r_coff != 0, in place in one concat buffer as YOLOv8's C2f issues it),
+# every activation / residual placement, bias or none, the output slice and its surroundings.
+# ---------------------------------------------------------------------------
+EPI_FAMILIES = {"v1": range(0, 6), "v2": range(6, STREAM0), "v3": range(STREAM0, DIRECT0),
+                "v4": range(DIRECT0, NLOOP0), "v6": range(NLOOP0, XP0), "v7": range(XP0, SK0),
+                "split-K": range(SK0, DE0), "v10": range(DE0, SKN0), "skinny": range(SKN0, PP0),
+                "ping-pong": range(PP0, N_TILES)}
+
+
+def _epi_accept(tile, case, variant):
+    """Must this tile run this (case, variant) -- and match -- or refuse it?  Built from the
+    family rules of test_conv_every_tile; tile -1 picks a v1 tile, which takes everything."""
+    cin, cout, k = epilogue_cases.CASES[case][:3]
+    act_bits, res, _ = epilogue_cases.VARIANTS[variant]
+    kpad = (cin * k * k + 63) // 64 * 64
+    if tile < STREAM0 or XP0 <= tile < DE0:     # v1, v2, v7, split-K: every conv
+        return True
+    if tile < DIRECT0:                          # v3: 1x1 stride-1 GEMMs that fit its LDS
+        return k == 1 and _stream_fits(tile, kpad, res)
+    if tile < NLOOP0:                           # v4: its instantiation table
+        return _v4_takes(cin, cout, k, 1, act_bits, res)
+    if tile < XP0:                              # v6: 1x1 GEMMs of the tile's own Kpad
+        return k == 1 and tile not in NLOOP_DUAL and kpad == NLOOP_KPAD[tile - NLOOP0]
+    if tile < SKN0:                             # v10: its own table, no fallback
+        return _de_takes(tile, cin, cout, k, 1, act_bits & 3, res) and _direct_res_form(act_bits, res)
+    return cin % 64 == 0                        # skinny, ping-pong: no generic gather
+
+
+def _epi_accepting(case, variant, family):
+    return [t for t in EPI_FAMILIES[family] if _epi_accept(t, case, variant)]
+
+
+# refusals must not hide a gap: checked when the module is collected
+for _c in epilogue_cases.CASES:
+    for _v in epilogue_cases.VARIANTS:
+        assert _epi_accept(-1, _c, _v), (_c, _v)
+for _f in ("v1", "v2", "v4", "v7", "split-K", "v10", "skinny", "ping-pong"):
+    assert _epi_accepting("c2f64", "silu_post", _f), _f
+for _v, (_a, _r, _b) in epilogue_cases.VARIANTS.items():
+    if _r:
+        assert _epi_accepting("gemm512", _v, "v3"), _v
+        assert _epi_accepting("gemm512", _v, "v6") == [
+            t for t in EPI_FAMILIES["v6"] if NLOOP_KPAD[t - NLOOP0] == 256 and t not in NLOOP_DUAL]
+    assert _epi_accept(NLOOP0, "gemm136", _v), _v
+
+
+def _epi_gpu_inputs(c):
+    if "gpu" not in c:
+        c["gpu"] = {k: None if c[k] is None else c[k].cuda() for k in ("x", "w", "b", "res")}
+    return c["gpu"]
+
+
+def _epi_launch(c, tile):
+    """One conv2d of the built case c on the GPU: the destination (CPU copy) after the call
+    and the NaN canary tail after it (separate-destination cases)."""
+    g = _epi_gpu_inputs(c)
+    n_out = c["dst0"].numel()
+    flat = torch.full((n_out + 4096,), float("nan"), dtype=torch.bfloat16, device="cuda")
+    dst = flat[:n_out].view(c["dst0"].shape)
+    dst.copy_(c["dst0"])
+    res = g["res"]
+    if c["in_place"] and res is not None:
+        res = dst
+    if ops.is_splitk(tile):  # no output may depend on the workspace's old contents
+        spec = c["spec"]
+        ops.splitk_workspace(dst.device, n_out // dst.shape[-1] * spec.cout).fill_(float("nan"))
+    ops.conv2d(g["x"], c["spec"], g["w"], g["b"], res=res, out=dst, r_coff=c["r_coff"],
+               y_coff=c["y_coff"], tile=tile)
+    torch.cuda.synchronize()
+    return dst.cpu(), flat[n_out:].cpu()
+
+
+def _epi_check(c, got, tail, exact, ctx):
+    yc, cout = c["y_coff"], c["cout"]
+    inside = got[..., yc:yc + cout]
+    if exact:
+        # the precondition is on the reference: every partial sum is an exact integer
+        assert c["bound"] <= epilogue_cases.EXACT_BOUND, (ctx, c["bound"])
+        assert torch.equal(c["ref"][..., yc:yc + cout].double(), c["ref64"]), ctx
+        bad = (inside.double() != c["ref64"])
+        assert torch.equal(inside.double(), c["ref64"]), (
+            ctx, int(bad.sum()), (inside.double() - c["ref64"])[bad][:8].tolist())
+    else:
+        _assert_close(inside, c["ref"][..., yc:yc + cout], ctx)
+    # everything around the written slice keeps its bits: the residual slice and slice 0 of
+    # the concat buffer, or the NaN fill of a separate destination and the tail after it
+    assert epilogue_cases.same_bits(epilogue_cases.outside(got, yc, cout),
+                                    epilogue_cases.outside(c["dst0"], yc, cout)), ctx
+    assert torch.isnan(tail.float()).all(), ctx
+
+
+@pytest.mark.parametrize("tile", [-1] + list(range(N_TILES)))
+def test_conv_epilogue_matrix(tile):
+    """Every tile x case x variant (sliced / in-place residual, act x residual placement, bias
+    or none, output slice with its surroundings): a tile the mirror says accepts must run
+    and match -- bit for bit against float64 on the integer (NONE / RELU) variants, within
+    the file's tolerances on the SiLU ones -- and a tile it says refuses must be refused by
+    its launcher.  One test per tile (the 49 combinations are a loop: thousands of test ids
+    for a few milliseconds each cost more than they tell); every failing combination is
+    reported, and the loop ends at the first error that is not a launcher's refusal."""
+    bad = []
+    for case in epilogue_cases.CASES:
+        for variant in epilogue_cases.VARIANTS:
+            c = epilogue_cases.build(case, variant)
+            accept = _epi_accept(tile, case, variant)
+            try:
+                got, tail = _epi_launch(c, tile)
+            except RuntimeError as e:
+                if "kv_conv2d failed rc=" not in str(e):
+                    raise  # not a refusal: nothing more may run on the GPU after it
+                if accept:
+                    bad.append((case, variant, "refused a call it must take", str(e)[-40:]))
+                continue
+            if not accept:
+                bad.append((case, variant, "ran a call it must refuse"))
+                continue
+            try:
+                _epi_check(c, got, tail, epilogue_cases.is_exact(variant), (tile, case, variant))
+            except AssertionError as e:
+                bad.append((case, variant, str(e)[:300]))
+    assert not bad, (tile, len(bad), bad)
+
+
+def _epi_chunk_params():
+    out = []
+    for v in ("silu_post", "relu_res"):
+        out.append((-1, v))
+        for f in ("v1", "v2", "v4", "v7", "split-K", "v10", "skinny", "ping-pong"):
+            acc = _epi_accepting("c2f64", v, f)
+            if acc:  # v4 and v10 compute no ReLU(conv + res): nothing of theirs to chunk
+                out.append((acc[0], v))
+    return out
+
+
+assert len(_epi_chunk_params()) == 9 + 7
+
+
+@pytest.mark.parametrize("tile,variant", _epi_chunk_params())
+def test_conv_chunked_sliced_residual(tile, variant):
+    """kv_conv2d's image-chunk path advances res by one image of ITS row pitch: c2f64 at
+    N = 3 with the chunk size at 160 KiB (one image of the 256-channel concat buffer is
+    73 216 B) runs as 2 + 1 images, and must equal the single launch bit for bit."""
+    c = epilogue_cases.build("c2f64", variant, n=3)
+    whole, tail = _epi_launch(c, tile)
+    _epi_check(c, whole, tail, epilogue_cases.is_exact(variant), ("single", tile, variant))
+    try:
+        assert torch.ops.kvedge.set_conv_chunk_bytes(160 << 10) == 160 << 10
+        chunked, tail = _epi_launch(c, tile)
+    finally:
+        torch.ops.kvedge.set_conv_chunk_bytes(0)
+    assert epilogue_cases.same_bits(chunked, whole), (tile, variant)
+    assert torch.isnan(tail.float()).all()
+
+
+@pytest.mark.parametrize("r_coff,y_coff", [(64, 96), (128, 96), (64, 64)])
+def test_conv_overlapping_residual_and_output_refused(r_coff, y_coff):
+    """res and out in one buffer with overlapping channel slices (partially, or identical):
+    one workgroup would read channels another writes, so ops.conv2d refuses before a launch."""
+    c = epilogue_cases.build("c2f64", "silu_post")
+    g = _epi_gpu_inputs(c)
+    cat = c["dst0"].cuda()
+    before = cat.clone()
+    with pytest.raises(ValueError, match="overlap"):
+        ops.conv2d(g["x"], c["spec"], g["w"], g["b"], res=cat, out=cat, r_coff=r_coff, y_coff=y_coff)
+    torch.cuda.synchronize()
+    assert torch.equal(cat, before)

@@ -3,6 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import epilogue_cases
 from kvedge_amd import ops
 from kvedge_amd.ops import ConvSpec
 
@@ -44,6 +45,45 @@ def test_reference_conv_matches_torch_and_slices():
                    2, 1).relu().permute(0, 2, 3, 1)
     assert (out[..., 16:64].float() - ref).abs().max() < 0.05
     assert out[..., :16].abs().sum() == 0 and out[..., 64:].abs().sum() == 0
+
+
+@pytest.mark.parametrize("variant", epilogue_cases.EXACT_VARIANTS)
+@pytest.mark.parametrize("case", list(epilogue_cases.CASES))
+def test_reference_conv_epilogue_exact(case, variant):
+    """The oracle of the kernel suite's epilogue matrix, before it judges a kernel: on the
+    exact (integer) construction the CPU reference equals the float64 result bit for bit --
+    residual read from its own channel slice, before / after the activation, bias or none,
+    in place in the C2f cases -- the stated bound holds, and every channel outside the
+    written slice keeps its bits."""
+    c = epilogue_cases.build(case, variant)
+    assert c["bound"] <= epilogue_cases.EXACT_BOUND, (case, variant, c["bound"])
+    yc, cout = c["y_coff"], c["cout"]
+    assert torch.equal(c["ref"][..., yc:yc + cout].double(), c["ref64"])
+    assert c["ref64"].abs().max().item() <= epilogue_cases.EXACT_BOUND
+    assert epilogue_cases.same_bits(epilogue_cases.outside(c["ref"], yc, cout),
+                                    epilogue_cases.outside(c["dst0"], yc, cout))
+    if c["res"] is not None:
+        # a residual read from another slice, or a dropped one, gives another result
+        spec, rc = c["spec"], c["r_coff"]
+        for other in (0, rc + 8):
+            wrong = c["dst0"].clone()
+            ops.conv2d(c["x"], spec, c["w"], c["b"], res=c["res"], out=wrong, r_coff=other,
+                       y_coff=yc)
+            assert not torch.equal(wrong[..., yc:yc + cout], c["ref"][..., yc:yc + cout])
+
+
+@pytest.mark.parametrize("r_coff,y_coff", [(16, 32), (32, 16), (24, 24)])
+def test_conv_overlapping_residual_and_output_refused(r_coff, y_coff):
+    """res and out in one buffer: the slices [r_coff, r_coff + cout) and [y_coff, y_coff + cout)
+    must be disjoint (a kernel's workgroups would read channels that others write)."""
+    spec = ConvSpec.auto(16, 24, 1, 1, 0, ops.ACT_RELU)
+    x = torch.zeros(1, 4, 4, 16, dtype=torch.bfloat16)
+    w = ops.pack_conv_weight(torch.zeros(24, 16, 1, 1), spec)
+    cat = torch.zeros(1, 4, 4, 64, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="overlap"):
+        ops.conv2d(x, spec, w, None, res=cat, out=cat, r_coff=r_coff, y_coff=y_coff)
+    ops.conv2d(x, spec, w, None, res=cat, out=cat, r_coff=0, y_coff=24)      # adjacent: fine
+    ops.conv2d(x, spec, w, None, res=cat.clone(), out=cat, r_coff=24, y_coff=24)  # two buffers
 
 
 def test_stem_reference_ignores_pad_channel():
