@@ -785,6 +785,48 @@ void roi_crop_nv12(const at::Tensor& src, const at::Tensor& det, const at::Tenso
   roi_crop_nv12_band(src, det, count, dst, pad, 0);
 }
 
+// K18: IoU tracker update (csrc/kernels/track.hip).  state int32 [S, 12 T + 4]; batch row n of
+// det / count is the next frame of stream slot0 + n
+void track_update(const at::Tensor& det, const at::Tensor& count, at::Tensor& state,
+                  at::Tensor& track_id, int64_t slot0, int64_t thr_q, int64_t max_age,
+                  int64_t min_hits, bool class_aware) {
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(state, "state");
+  check_dev(track_id, "track_id");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6,
+              "kvedge: det fp32 [N,max_det,6]");
+  const int64_t N = det.size(0), max_det = det.size(1);
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == N,
+              "kvedge: count int32 [N]");
+  TORCH_CHECK(track_id.scalar_type() == at::kInt && track_id.dim() == 2 &&
+                  track_id.size(0) == N && track_id.size(1) == max_det,
+              "kvedge: track_id int32 [N,max_det]");
+  TORCH_CHECK(state.scalar_type() == at::kInt && state.dim() == 2 && state.size(1) >= 4 &&
+                  (state.size(1) - 4) % 12 == 0, "kvedge: track state int32 [S, 12*T+4]");
+  const int64_t S = state.size(0), T = (state.size(1) - 4) / 12;
+  TORCH_CHECK(T == 64 || T == 128 || T == 192 || T == 256,
+              "kvedge: track_update max_tracks is 64, 128, 192 or 256, got ", T);
+  TORCH_CHECK(state.size(1) == kv_track_state_stride((int)T), "kvedge: track state row size");
+  TORCH_CHECK(S < (1ll << 24) && N < (1ll << 24), "kvedge: track_update too many streams");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: track_update streams [", slot0, ", ",
+              slot0 + N, ") outside the state's ", S);
+  TORCH_CHECK(max_det >= 1 && max_det <= 300, "kvedge: track_update max_det is 1..300, got ",
+              max_det);
+  TORCH_CHECK(max_age >= 0 && max_age <= 255, "kvedge: track_update max_age is 0..255");
+  TORCH_CHECK(min_hits >= 1 && min_hits <= 255, "kvedge: track_update min_hits is 1..255");
+  TORCH_CHECK(thr_q >= 1 && thr_q <= 1024, "kvedge: track_update thr_q is 1..1024");
+  TORCH_CHECK(det.device() == count.device() && det.device() == state.device() &&
+                  det.device() == track_id.device(),
+              "kvedge: track_update operands on different devices");
+  const c10::DeviceGuard g(det.device());
+  const int rc = kv_track_update(det.data_ptr<float>(), count.data_ptr<int>(),
+                                 state.data_ptr<int>(), track_id.data_ptr<int>(), (int)N, (int)S,
+                                 (int)slot0, (int)T, (int)max_det, (int)thr_q, (int)max_age,
+                                 (int)min_hits, class_aware ? 1 : 0, cur_stream(det));
+  TORCH_CHECK(rc == 0, "kvedge: track_update failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -905,6 +947,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("frame_resize_nv12(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
   m.def("roi_crop_nv12(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad) -> ()");
   m.def("roi_crop_nv12_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
+  m.def("track_update(Tensor det, Tensor count, Tensor(a!) state, Tensor(b!) track_id, int slot0, "
+        "int thr_q, int max_age, int min_hits, bool class_aware) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -949,6 +993,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("frame_resize_nv12", frame_resize_nv12);
   m.impl("roi_crop_nv12", roi_crop_nv12);
   m.impl("roi_crop_nv12_band", roi_crop_nv12_band);
+  m.impl("track_update", track_update);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

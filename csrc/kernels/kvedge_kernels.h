@@ -189,6 +189,19 @@ int kv_roi_crop_nv12(const uint8_t* src, const float* det, const int* count, uin
 int kv_roi_crop_nv12_band(const uint8_t* src, const float* det, const int* count, uint8_t* dst,
                           int N, int Hs, int Ws, int max_det, int K, int D, int pad, int band,
                           hipStream_t s);
+// K18 (track.hip): one IoU-tracker update of streams [slot0, slot0 + N) of state int32
+// [S, kv_track_state_stride(T)] from the step's detections det fp32 [N,max_det,6] / count
+// int32 [N] (batch row n is the next frame of stream slot0 + n); track_id int32 [N,max_det]
+// gets each row's track id (-1: not confirmed, no free slot, or row >= count[n]), every
+// element written.  Integer arithmetic on quarter-pixel boxes, bit-identical to
+// ops.reference.track_update; the semantics and the state layout are at the top of track.hip.
+// thr_q = floor(iou * 1024 + 0.5).  Other streams of `state` are neither read nor written.
+// Returns -1 T not 64/128/192/256, -2 slot0 + N > S, -3 max_det outside 1..300, -4 max_age
+// outside 0..255, -5 min_hits outside 1..255, -6 thr_q outside 1..1024, -7 misaligned state.
+int kv_track_state_stride(int T);
+int kv_track_update(const float* det, const int* count, int* state, int* track_id, int N, int S,
+                    int slot0, int T, int max_det, int thr_q, int max_age, int min_hits,
+                    int class_aware, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

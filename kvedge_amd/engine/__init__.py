@@ -80,6 +80,10 @@ class InferenceEngine:
     decoders deliver them, ``source_frames`` is [B, Hs * 3 // 2, Ws] (half the bytes through
     the ring and over PCIe) and the resample converts each source tap to RGB on the way
     (ops.frame_resize(..., src_format="nv12")).  NV12 needs ``frame_hw``.
+    A model with ``stateful = True`` (models.tracking.KvTracked) keeps device state across steps,
+    one entry per batch row: it is called with ``slot0`` = the first batch row of the slice, its
+    state is left freshly reset by ``prepare()`` (``reset_tracks()`` does the same later), and
+    the state tensors live outside the captured graph's pool.
     """
 
     def __init__(self, model: Callable, batch: int, image_size: int, device="cuda",
@@ -164,15 +168,29 @@ class InferenceEngine:
         ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames, **fmt)
         if hasattr(self.model, "from_source"):
             return self.model.from_source(self.source_frames[lo:hi], frames, self.frame_plan,
-                                          **fmt)
-        out = self.model(frames)
+                                          **self._slot(lo), **fmt)
+        out = self.model(frames, **self._slot(lo))
         if hasattr(self.model, "to_source"):
             out = self.model.to_source(out, self.frame_plan)
         return out
 
+    def _slot(self, lo: int) -> dict:
+        """A stateful model (models.tracking.KvTracked: batch row n is camera n) is told which
+        batch rows a slice holds, so every slice updates its own streams; other models keep
+        their call signatures."""
+        return {"slot0": lo} if getattr(self.model, "stateful", False) else {}
+
+    def reset_tracks(self) -> None:
+        """Forget every track of a stateful model (ids restart at 0); a no-op for the others.
+        Device ops on the current stream, outside the captured graph."""
+        if getattr(self.model, "stateful", False):
+            self.model.reset()
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
+
     def _forward(self):
         if not self._side:
-            self.outputs = (self.model(self.frames) if self.frame_plan is None
+            self.outputs = (self.model(self.frames, **self._slot(0)) if self.frame_plan is None
                             else self._run_slice(0, self.batch))
             return self.outputs
         cur = torch.cuda.current_stream(self.device)
@@ -181,7 +199,8 @@ class InferenceEngine:
         for i, s in enumerate(self._side):
             s.wait_stream(cur)
             with torch.cuda.stream(s):
-                parts.append(self.model(self.frames[i * per:(i + 1) * per])
+                parts.append(self.model(self.frames[i * per:(i + 1) * per],
+                                        **self._slot(i * per))
                              if self.frame_plan is None
                              else self._run_slice(i * per, (i + 1) * per))
         for s in self._side:
@@ -224,6 +243,7 @@ class InferenceEngine:
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             self.prep_s["warmup"] = time.perf_counter() - t1
+            self.reset_tracks()  # the warm-up steps advanced a tracker's state
             return self
         self._cap_stream = s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -249,6 +269,9 @@ class InferenceEngine:
             self.refine = graph_refine(self, budget_s=refine_s, verbose=verbose,
                                        cache_path=tune_cache)
             self.prep_s["graph_refine"] = time.perf_counter() - t3
+        # tuning, warm-up and refinement ran the step eagerly or replayed it: a tracker's
+        # state (outside the graph's pool, persistent across replays) starts from zero
+        self.reset_tracks()
         return self
 
     def capture(self, warm: bool = True):

@@ -1,0 +1,76 @@
+"""Multi-object tracking on top of a detector: the same object keeps the same id from frame
+to frame.
+
+``KvTracked`` wraps a model whose outputs start with ``(det, count)`` (KvYoloV8n,
+KvDetectClassify) and appends ``track_id`` int32 [N, max_det] to them.  One batch row = one
+camera: with tracking on, row n of every batch is the next frame of stream ``slot0 + n``, so a
+module of batch B serves B cameras, one frame each per step.  The tracker state lives in
+device memory (ops.TrackState) and is updated by one kernel launch per step
+(ops.track_update, csrc/kernels/track.hip): no host in the loop, so the step stays one
+captured graph -- the state tensors are allocated here, outside the graph's pool, and persist
+across replays.
+"""
+from __future__ import annotations
+
+from typing import List
+
+import torch
+
+from .. import ops
+
+
+class KvTracked:
+    """inner outputs ``(det, count, ...)`` -> ``(det, count, ..., track_id)``.  Tracking runs
+    on the boxes as they are reported: frame pixels when the engine has a frame size
+    (``from_source``), model pixels otherwise."""
+
+    stateful = True  # InferenceEngine passes slot0 = first batch row of the slice
+
+    def __init__(self, inner, streams: int, iou: float = 0.3, max_age: int = 30,
+                 min_hits: int = 3, max_tracks: int = 64, class_aware: bool = True):
+        self.inner = inner
+        self.device = inner.device
+        self.iou, self.max_age, self.min_hits = float(iou), int(max_age), int(min_hits)
+        self.class_aware = bool(class_aware)
+        if not 1 <= ops.track_thr_q(self.iou) <= 1024:
+            raise ValueError(f"track iou {iou} outside (0, 1]")
+        if not 0 <= self.max_age <= 255:
+            raise ValueError(f"max_age {max_age} outside 0..255")
+        if not 1 <= self.min_hits <= 255:
+            raise ValueError(f"min_hits {min_hits} outside 1..255")
+        self.state = ops.TrackState(streams, max_tracks, self.device)
+        self.image_size = getattr(inner, "image_size", 640)
+
+    # -- what the engine, the autotuner and the module read off a model
+    def convs(self) -> List:
+        return self.inner.convs()
+
+    def flops_per_image(self, hw: int = 640) -> int:
+        return self.inner.flops_per_image(hw)
+
+    def frame_plan(self, src_hw, image_size: int = 0) -> "ops.ResizePlan":
+        return self.inner.frame_plan(src_hw, image_size)
+
+    def reset(self) -> None:
+        """Forget every track; ids restart at 0."""
+        self.state.reset()
+
+    def _track(self, out, slot0: int):
+        det, count = out[0], out[1]
+        tid = ops.track_update(det, count, self.state, slot0=slot0, iou=self.iou,
+                               max_age=self.max_age, min_hits=self.min_hits,
+                               class_aware=self.class_aware)
+        return (*out, tid)
+
+    def __call__(self, frames_u8: torch.Tensor, slot0: int = 0):
+        return self._track(tuple(self.inner(frames_u8)), slot0)
+
+    def from_source(self, source_frames: torch.Tensor, frames: torch.Tensor,
+                    plan: "ops.ResizePlan", slot0: int = 0, **fmt):
+        """Native-resolution serving: the inner model's boxes in frame pixels, then the
+        tracker on those."""
+        if hasattr(self.inner, "from_source"):
+            out = self.inner.from_source(source_frames, frames, plan, **fmt)
+        else:
+            out = self.inner.to_source(self.inner(frames), plan)
+        return self._track(tuple(out), slot0)

@@ -82,6 +82,17 @@ def main(argv=None):
     ap.add_argument("--crops-per-image", type=int, default=d.crops_per_image,
                     help="--model detect-classify: boxes per frame cut out and classified "
                          "(1..16, <= max_det)")
+    ap.add_argument("--track", action="store_true",
+                    help="--model yolov8n / detect-classify: track objects across frames "
+                         "(one batch row = one camera; telemetry gains `tracks`)")
+    ap.add_argument("--track-iou", type=float, default=d.track_iou,
+                    help="tracker association gate, IoU in (0, 1]")
+    ap.add_argument("--track-max-age", type=int, default=d.track_max_age,
+                    help="frames a lost track coasts before it is dropped (0..255)")
+    ap.add_argument("--track-min-hits", type=int, default=d.track_min_hits,
+                    help="consecutive matches before a track gets its id (1..255)")
+    ap.add_argument("--track-max-tracks", type=int, default=d.track_max_tracks,
+                    help="track slots per camera (64, 128, 192 or 256)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -116,7 +127,10 @@ def main(argv=None):
                        steps_per_poll=a.steps_per_poll, sync_every=a.sync_every,
                        refine_s=a.refine_s, frame_height=a.frame_height,
                        frame_width=a.frame_width,
-                       crops_per_image=a.crops_per_image).validate()
+                       crops_per_image=a.crops_per_image, track=a.track,
+                       track_iou=a.track_iou, track_max_age=a.track_max_age,
+                       track_min_hits=a.track_min_hits,
+                       track_max_tracks=a.track_max_tracks).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -418,6 +418,13 @@ class ModuleApp:
 
                 clf = KvResNet50.build(seed=cfg.seed, device=dev, calibrate=dev.type == "cuda")
                 self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
+            if cfg.track:
+                from ..models.tracking import KvTracked
+
+                # one batch row = one camera: `batch` streams
+                self.model = KvTracked(self.model, cfg.batch, iou=cfg.track_iou,
+                                       max_age=cfg.track_max_age, min_hits=cfg.track_min_hits,
+                                       max_tracks=cfg.track_max_tracks)
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -726,6 +733,10 @@ class ModuleApp:
             order = counts.argsort(descending=True)[:5]
             res["crops"] = int(cls.numel())
             res["crop_top1"] = {str(int(vals[i])): int(counts[i]) for i in order}
+        if self.cfg.track and getattr(self.model, "stateful", False):
+            st = self.model.state  # live tracks, distinct confirmed objects, lost detections
+            res["tracks"] = {"active": st.active(), "unique": st.unique(),
+                             "dropped": int(st.dropped.sum())}
         return res
 
     # ---------------------------------------------------------------- handlers

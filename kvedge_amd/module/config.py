@@ -46,6 +46,17 @@ class ModuleConfig:
     # device and classified (ResNet-50 at 224); the classifier runs batch * crops_per_image
     # images per step whatever the detection counts are
     crops_per_image: int = 4
+    # multi-object tracking (models "yolov8n" / "detect-classify"): ONE BATCH ROW = ONE CAMERA
+    # -- row n of every batch is the next frame of camera n, so the module serves `batch`
+    # cameras, one frame each per step -- and every detection gets the id of the track it
+    # continues (on-device IoU tracker, ops.track_update).  track_iou: association gate;
+    # track_max_age: frames a lost track coasts before it is dropped; track_min_hits:
+    # consecutive matches before a track gets its id; track_max_tracks: slots per camera
+    track: bool = False
+    track_iou: float = 0.3
+    track_max_age: int = 30
+    track_min_hits: int = 3
+    track_max_tracks: int = 64
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -64,7 +75,8 @@ class ModuleConfig:
 
     # keys that force an engine rebuild when they change
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
-               "use_graph", "source", "frame_height", "frame_width", "crops_per_image")
+               "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
+               "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
 
     def validate(self) -> "ModuleConfig":
         if self.model not in MODELS:
@@ -105,6 +117,17 @@ class ModuleConfig:
                 raise ValueError("crops_per_image must be <= max_det")
             if self.batch * self.crops_per_image > 4096:
                 raise ValueError("batch * crops_per_image must be <= 4096")
+        # the tracker launcher's ranges (csrc/kernels/track.hip); the gate is kept in 1/1024
+        if not 1 <= int(self.track_iou * 1024 + 0.5) <= 1024:
+            raise ValueError("track_iou must be in (0, 1] (at least 1/2048)")
+        if not 0 <= self.track_max_age <= 255:
+            raise ValueError("track_max_age must be 0..255")
+        if not 1 <= self.track_min_hits <= 255:
+            raise ValueError("track_min_hits must be 1..255")
+        if self.track_max_tracks not in (64, 128, 192, 256):
+            raise ValueError("track_max_tracks must be 64, 128, 192 or 256")
+        if self.track and self.model not in ("yolov8n", "detect-classify"):  # binds only when on
+            raise ValueError("track needs a detector: model yolov8n or detect-classify")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -153,5 +176,15 @@ class ModuleConfig:
         """Format of the incoming frames (InferenceEngine frame_format)."""
         return "nv12" if self.source == "camera-nv12" else "rgb"
 
+    TRACK_KEYS = ("track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
+
     def to_dict(self) -> Dict[str, Any]:
-        return asdict(self)
+        """The reported / saved config.  The tracking keys are listed once any of them has
+        left its default: a module that was never asked to track reports exactly the config
+        it reported before tracking existed."""
+        d = asdict(self)
+        base = ModuleConfig()
+        if all(getattr(self, k) == getattr(base, k) for k in self.TRACK_KEYS):
+            for k in self.TRACK_KEYS:
+                d.pop(k)
+        return d

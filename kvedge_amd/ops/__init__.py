@@ -915,6 +915,116 @@ def roi_crop_nv12(src: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: 
     return roi_crop(src, det, count, k, size, pad=pad, out=out, band=band, src_format="nv12")
 
 
+# ---------------------------------------------------------------------------
+# multi-object tracking: detections -> stable ids across frames
+# ---------------------------------------------------------------------------
+TRACK_MAX_TRACKS = (64, 128, 192, 256)  # slots per stream: 1..4 per lane of one wavefront
+TRACK_MAX_DET = 300
+TRACK_FIELDS = ("box", "vel", "cls", "id", "age", "hits", "next_id", "dropped")
+
+
+class TrackState:
+    """Tracker state of ``streams`` cameras with ``max_tracks`` slots each, one int32 buffer
+    ``buf`` [streams, 12 * max_tracks + 4] (the layout csrc/kernels/track.hip reads:
+    box | vel | cls | id | age | hits | next_id, dropped, 0, 0) and named views into it:
+    ``box`` / ``vel`` [S, T, 4] (quarter pixels; per frame), ``cls`` / ``id`` / ``age`` /
+    ``hits`` [S, T] (id -1 = not confirmed, hits 0 = free slot), ``next_id`` / ``dropped``
+    [S] (ids handed out so far = distinct confirmed objects; detections that found no slot)."""
+
+    def __init__(self, streams: int, max_tracks: int = 64, device="cpu"):
+        if max_tracks not in TRACK_MAX_TRACKS:
+            raise ValueError(f"max_tracks must be one of {TRACK_MAX_TRACKS}, got {max_tracks}")
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+        T = self.max_tracks
+        self.buf = torch.zeros(self.streams, 12 * T + 4, dtype=torch.int32, device=device)
+        self.box = self.buf[:, :4 * T].unflatten(1, (T, 4))
+        self.vel = self.buf[:, 4 * T:8 * T].unflatten(1, (T, 4))
+        self.cls = self.buf[:, 8 * T:9 * T]
+        self.id = self.buf[:, 9 * T:10 * T]
+        self.age = self.buf[:, 10 * T:11 * T]
+        self.hits = self.buf[:, 11 * T:12 * T]
+        self.next_id = self.buf[:, 12 * T]
+        self.dropped = self.buf[:, 12 * T + 1]
+        self.reset()
+
+    @property
+    def device(self) -> torch.device:
+        return self.buf.device
+
+    def reset(self) -> "TrackState":
+        """Forget every track and restart the ids at 0 (device ops on the current stream)."""
+        self.buf.zero_()
+        self.id.fill_(-1)
+        return self
+
+    def active(self) -> int:
+        """Live tracks over all streams, tentative ones included (syncs with the device)."""
+        return int((self.hits > 0).sum())
+
+    def unique(self) -> int:
+        """Distinct confirmed objects so far over all streams (syncs with the device)."""
+        return int(self.next_id.sum())
+
+
+def track_thr_q(iou: float) -> int:
+    """The IoU gate in 1/1024: floor(iou * 1024 + 0.5) (0.3 -> 307)."""
+    import math
+
+    return int(math.floor(float(iou) * 1024 + 0.5))
+
+
+def track_update(det: torch.Tensor, count: torch.Tensor, state: TrackState, slot0: int = 0,
+                 iou: float = 0.3, max_age: int = 30, min_hits: int = 3,
+                 class_aware: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One tracker step: batch row n of ``det`` fp32 [N, max_det, 6] / ``count`` int32 [N]
+    (:func:`nms` output, in any pixel frame that stays the same from step to step) is the next
+    frame of stream ``slot0 + n`` of ``state``.  Returns ``track_id`` int32 [N, max_det]: the
+    id of the track each row continues or starts, -1 while the track is not confirmed
+    (fewer than ``min_hits`` consecutive matches), when no slot was free, and for rows
+    >= count[n].  A track coasts on its last velocity for up to ``max_age`` missed frames.
+    ``iou``: the association gate; ``class_aware``: a detection only continues a track of its
+    class.  Integer arithmetic on quarter-pixel boxes: GPU (csrc/kernels/track.hip) and CPU
+    (ops.reference.track_update, where the rules are written out) are bit-identical.  Streams
+    outside [slot0, slot0 + N) are not touched."""
+    if not isinstance(state, TrackState):
+        raise TypeError(f"state must be an ops.TrackState, got {type(state).__name__}")
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6:
+        raise ValueError(f"det must be fp32 [N, max_det, 6], got {det.dtype} {tuple(det.shape)}")
+    n, max_det = int(det.shape[0]), int(det.shape[1])
+    if count.dtype != torch.int32 or tuple(count.shape) != (n,):
+        raise ValueError(f"count must be int32 [{n}], got {count.dtype} {tuple(count.shape)}")
+    if not det.is_contiguous() or not count.is_contiguous():
+        raise ValueError("det and count must be contiguous")
+    if det.device != state.device or count.device != state.device:
+        raise ValueError(f"det / count on {det.device} / {count.device}, state on {state.device}")
+    if not 1 <= max_det <= TRACK_MAX_DET:
+        raise ValueError(f"track_update needs 1 <= max_det <= {TRACK_MAX_DET}, got {max_det}")
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > state.streams:
+        raise ValueError(f"streams [{slot0}, {slot0 + n}) outside the state's {state.streams}")
+    if not 0 <= int(max_age) <= 255:
+        raise ValueError(f"max_age {max_age} outside 0..255")
+    if not 1 <= int(min_hits) <= 255:
+        raise ValueError(f"min_hits {min_hits} outside 1..255")
+    thr_q = track_thr_q(iou)
+    if not 1 <= thr_q <= 1024:
+        raise ValueError(f"iou {iou} gives a threshold of {thr_q}/1024, outside 1..1024")
+    if out is None:
+        out = empty(n, max_det, dtype=torch.int32, device=det.device)
+    if (out.dtype != torch.int32 or tuple(out.shape) != (n, max_det) or not out.is_contiguous()
+            or out.device != det.device):
+        raise ValueError(f"out must be contiguous int32 [{n}, {max_det}] on {det.device}")
+    if det.is_cuda:
+        _native().track_update(det, count, state.buf, out, slot0, thr_q, int(max_age),
+                               int(min_hits), bool(class_aware))
+    else:
+        _ref.track_update(det, count, state, slot0, thr_q, int(max_age), int(min_hits),
+                          bool(class_aware), out)
+    return out
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

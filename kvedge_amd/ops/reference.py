@@ -267,6 +267,115 @@ def roi_crop(src, det, count, K, D, pad, out):
     return out
 
 
+TRACK_Q_MAX = 16384  # quarter pixels: 4096 px, the largest frame the module accepts
+
+
+def track_quantize(x):
+    """fp32 coordinates -> quarter pixels, int64: q(x) = min(max(floor(x * 4 + 0.5), 0), 16384)
+    in fp32 with NaN -> 0 (the kernel's fmaxf(NaN, 0)); x * 4 is exact."""
+    v = torch.floor(x.float() * 4.0 + 0.5)
+    v = torch.nan_to_num(v, nan=0.0, posinf=float(TRACK_Q_MAX), neginf=0.0)
+    return v.clamp(0.0, float(TRACK_Q_MAX)).to(torch.int64)
+
+
+def track_class(c):
+    """fp32 class column of det -> int64 (clamped to 0..65535, NaN -> 0, truncated)."""
+    v = torch.nan_to_num(c.float(), nan=0.0, posinf=65535.0, neginf=0.0)
+    return v.clamp(0.0, 65535.0).to(torch.int64)
+
+
+def _box_area(b):
+    return (b[..., 2] - b[..., 0]).clamp_min(0) * (b[..., 3] - b[..., 1]).clamp_min(0)
+
+
+def track_update(det, count, state, slot0, thr_q, max_age, min_hits, class_aware, out):
+    """One IoU-tracker update: THE definition the HIP kernel (csrc/kernels/track.hip) equals
+    bit for bit.  det fp32 [N, max_det, 6] / count int32 [N]: row n is the next frame of stream
+    ``slot0 + n`` of ``state`` (an ops.TrackState on the CPU; its views are updated in place);
+    out int32 [N, max_det] gets every row's track id.  Per stream, in this order:
+
+    1. predict: slots live at entry (hits > 0): pred = clamp(box + vel * (age + 1), 0, 16384);
+    2. associate: rows r < count in order (NMS orders them by score); a slot is a candidate when
+       it was live at entry, is not claimed yet, has the row's class (``class_aware``),
+       inter > 0 and inter * 1024 >= thr_q * union (int64, no divide); the best is the largest
+       inter / union by cross-multiplication, the lower slot on equality.  Match:
+       vel = trunc((q(det) - box) / (age + 1)), box = q(det), age = 0, hits += 1, cls = row's;
+       an unconfirmed track (id < 0) with hits >= min_hits gets id = next_id++;
+    3. age: live at entry and unclaimed: age += 1; freed (all zero, id -1) when age > max_age
+       or while still unconfirmed;
+    4. birth: unmatched rows in order take the lowest free slot (box = q(det), vel 0, age 0,
+       hits 1; id = next_id++ only when min_hits <= 1); none free: id -1, dropped += 1;
+    5. out[n, r] = -1 for r >= count[n] (count clamped to 0..max_det)."""
+    N, max_det, _ = det.shape
+    i32 = torch.int32
+    for n in range(N):
+        s = slot0 + n
+        box, vel = state.box[s].long(), state.vel[s].long()
+        cls, tid = state.cls[s].long(), state.id[s].long()
+        age, hits = state.age[s].long(), state.hits[s].long()
+        next_id, dropped = int(state.next_id[s]), int(state.dropped[s])
+        cnt = min(max(int(count[n]), 0), max_det)
+        dq = track_quantize(det[n, :cnt, :4])
+        dc = track_class(det[n, :cnt, 5])
+        live = hits > 0
+        pred = (box + vel * (age + 1).unsqueeze(1)).clamp(0, TRACK_Q_MAX)
+        parea = _box_area(pred)
+        claimed = torch.zeros_like(live)
+        ids = torch.full((max_det,), -1, dtype=torch.int64)
+        unmatched = []
+        for r in range(cnt):
+            d = dq[r]
+            iw = (torch.minimum(pred[:, 2], d[2]) - torch.maximum(pred[:, 0], d[0])).clamp_min(0)
+            ih = (torch.minimum(pred[:, 3], d[3]) - torch.maximum(pred[:, 1], d[1])).clamp_min(0)
+            inter = iw * ih
+            union = parea + _box_area(d) - inter
+            cand = live & ~claimed & (inter > 0) & (inter * 1024 >= thr_q * union)
+            if class_aware:
+                cand &= cls == dc[r]
+            idx = cand.nonzero().flatten()
+            if idx.numel() == 0:
+                unmatched.append(r)
+                continue
+            ci, cu = inter[idx], union[idx]
+            # beaten[i]: some candidate j has inter_j / union_j > inter_i / union_i
+            beaten = (ci.view(1, -1) * cu.view(-1, 1) > ci.view(-1, 1) * cu.view(1, -1)).any(1)
+            m = int(idx[(~beaten).nonzero()[0, 0]])  # lowest slot among the best
+            vel[m] = torch.div(d - box[m], age[m] + 1, rounding_mode="trunc")
+            box[m] = d
+            age[m] = 0
+            hits[m] += 1
+            cls[m] = dc[r]
+            if tid[m] < 0 and hits[m] >= min_hits:
+                tid[m] = next_id
+                next_id += 1
+            claimed[m] = True
+            ids[r] = tid[m]
+        missed = live & ~claimed
+        age[missed] += 1
+        free = missed & ((age > max_age) | (tid < 0))
+        box[free], vel[free] = 0, 0
+        cls[free], age[free], hits[free] = 0, 0, 0
+        tid[free] = -1
+        for r in unmatched:
+            empty = (hits == 0).nonzero().flatten()
+            if empty.numel() == 0:
+                dropped += 1
+                continue
+            m = int(empty[0])
+            box[m], vel[m] = dq[r], 0
+            cls[m], age[m], hits[m] = dc[r], 0, 1
+            if min_hits <= 1:
+                tid[m] = next_id
+                next_id += 1
+            ids[r] = tid[m]
+        state.box[s], state.vel[s] = box.to(i32), vel.to(i32)
+        state.cls[s], state.id[s] = cls.to(i32), tid.to(i32)
+        state.age[s], state.hits[s] = age.to(i32), hits.to(i32)
+        state.next_id[s], state.dropped[s] = next_id, dropped
+        out[n] = ids.to(i32)
+    return out
+
+
 def conv_dual2(x, x_coff, K1, x2, x2_coff, w, bias, act, stride2, up2, out, y_coff):
     K2 = w.shape[1] - K1
     a = x[..., x_coff:x_coff + K1].float()
