@@ -28,6 +28,22 @@ void check_bf16(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16, "kvedge: ", name, " must be bf16");
 }
 
+// Channel-slice contract of maxpool2d / upsample2x (kvedge_amd.ops._check_slices): x is
+// [N,H,W,ldx], y is [N,Ho,Wo,ldy], both slices lie inside their rows, everything in 16-B units.
+void check_slices(const char* op, const at::Tensor& x, const at::Tensor& y, int64_t N, int64_t H,
+                  int64_t W, int64_t C, int64_t ldx, int64_t x_coff, int64_t ldy, int64_t y_coff,
+                  int64_t Ho, int64_t Wo) {
+  TORCH_CHECK(x.dim() == 4 && x.size(0) == N && x.size(1) == H && x.size(2) == W && x.size(3) == ldx,
+              "kvedge: ", op, " x must be [N,H,W,ldx]");
+  TORCH_CHECK(y.dim() == 4 && y.size(0) == N && y.size(1) == Ho && y.size(2) == Wo && y.size(3) == ldy,
+              "kvedge: ", op, " y must be [N,Ho,Wo,ldy]");
+  TORCH_CHECK(C > 0 && x_coff >= 0 && y_coff >= 0 && C % 8 == 0 && ldx % 8 == 0 && x_coff % 8 == 0 &&
+                  ldy % 8 == 0 && y_coff % 8 == 0,
+              "kvedge: ", op, " C, ldx, x_coff, ldy, y_coff must be multiples of 8");
+  TORCH_CHECK(x_coff + C <= ldx, "kvedge: ", op, " input slice exceeds ldx");
+  TORCH_CHECK(y_coff + C <= ldy, "kvedge: ", op, " output slice exceeds ldy");
+}
+
 // Split-K workspace: fp32 slabs, one per K slice of the tile ([ksplit][M][Cout]); the
 // launcher refuses a tile whose slabs do not fit (ops.splitk_workspace sizes it per tile).
 void set_splitk_ws(KvConvParams& p, const at::Tensor& ws) {
@@ -354,7 +370,10 @@ void maxpool2d(const at::Tensor& x, at::Tensor& y, int64_t N, int64_t H, int64_t
                int64_t Ho, int64_t Wo) {
   check_bf16(x, "x");
   check_bf16(y, "y");
-  TORCH_CHECK(x.numel() >= N * H * W * ldx && y.numel() >= N * Ho * Wo * ldy, "kvedge: maxpool sizes");
+  check_slices("maxpool2d", x, y, N, H, W, C, ldx, x_coff, ldy, y_coff, Ho, Wo);
+  TORCH_CHECK(k >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= k && W + 2 * pad >= k &&
+                  Ho == (H + 2 * pad - k) / stride + 1 &&
+                  Wo == (W + 2 * pad - k) / stride + 1, "kvedge: maxpool2d output size");
   const c10::DeviceGuard g(x.device());
   const int rc = kv_maxpool2d(x.data_ptr(), y.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)ldx,
                               (int)x_coff, (int)ldy, (int)y_coff, (int)k, (int)stride, (int)pad, (int)Ho,
@@ -435,7 +454,7 @@ void upsample2x(const at::Tensor& x, at::Tensor& y, int64_t N, int64_t H, int64_
                 int64_t ldx, int64_t x_coff, int64_t ldy, int64_t y_coff) {
   check_bf16(x, "x");
   check_bf16(y, "y");
-  TORCH_CHECK(x.numel() >= N * H * W * ldx && y.numel() >= N * 4 * H * W * ldy, "kvedge: upsample sizes");
+  check_slices("upsample2x", x, y, N, H, W, C, ldx, x_coff, ldy, y_coff, 2 * H, 2 * W);
   const c10::DeviceGuard g(x.device());
   const int rc = kv_upsample2x(x.data_ptr(), y.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)ldx,
                                (int)x_coff, (int)ldy, (int)y_coff, cur_stream(x));

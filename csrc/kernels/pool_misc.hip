@@ -310,8 +310,8 @@ __global__ __launch_bounds__(kBlock) void softmax_kernel(const bf16* __restrict_
 
 // ---- K8 nearest 2x upsample into a channel slice ---------------------------
 // One thread per SOURCE 16-B vector: one load, four stores (the 2x2 block it
-// feeds).  32-bit index math (host checks N*H*W*C/8 < 2^31); the grid is sized to
-// the work, so each thread runs its body at most a few times.
+// feeds).  32-bit index math (host checks N*H*W*C/8 + one grid stride < 2^31); the
+// grid is sized to the work, so each thread runs its body at most a few times.
 __global__ __launch_bounds__(kBlock) void upsample2x_kernel(const bf16* __restrict__ x,
                                                             bf16* __restrict__ y, int N, int H,
                                                             int W, int C, int ldx, int x_coff,
@@ -487,6 +487,9 @@ extern "C" int kv_maxpool2d(const void* x, void* y, int N, int H, int W, int C, 
 
 extern "C" int kv_sppf_pool(void* buf, int N, int H, int W, int C, hipStream_t s) {
   if (C % kSppfCg) return -1;
+  // Launches above 64 KiB of dynamic LDS (33x32 .. 40x64 maps, up to the 160 KiB cap) run and
+  // are exact on gfx950 without a hipFuncSetAttribute(MaxDynamicSharedMemorySize) call:
+  // tests/test_pool_misc_gpu.py::test_sppf_exact.
   const long long lds = 2LL * H * W * kSppfCg * 2;
   if (lds > 160 * 1024) return -2;  // 2 LDS images of the 16-channel slice must fit
   const long long g = (long long)N * (C / kSppfCg);
@@ -530,7 +533,9 @@ extern "C" int kv_upsample2x(const void* x, void* y, int N, int H, int W, int C,
                              int x_coff, int ldy, int y_coff, hipStream_t s) {
   if (C % 8 || ldx % 8 || x_coff % 8 || ldy % 8 || y_coff % 8) return -1;
   const long long work = (long long)N * H * W * (C / 8);
-  if (work >= (1ll << 31)) return -1;
+  // the kernel's int index takes one more grid stride (at most 8192 * kBlock) past the last
+  // item before its loop test: that sum, too, must stay below 2^31
+  if (work + 8192ll * kBlock >= (1ll << 31)) return -1;
   long long g = (work + kBlock - 1) / kBlock;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)(g < 1 ? 1 : g)), dim3(kBlock), 0, s,

@@ -565,6 +565,23 @@ def stem_from_frames(frames: torch.Tensor, spec: "ConvSpec", w: torch.Tensor,
     return conv2d(x, spec, w, bias, out=out)
 
 
+def _check_slices(op: str, C: int, ldx: int, x_coff: int, out: torch.Tensor, y_coff: int,
+                  out_nhw: Tuple[int, int, int]) -> None:
+    """The channel-slice contract of maxpool2d / upsample2x, the same on both paths: the
+    kernels move 8 channels (16 B) per access and trust the slices to lie inside their rows."""
+    ldy = out.shape[3] if out.dim() == 4 else -1
+    if out.dim() != 4 or tuple(out.shape[:3]) != tuple(out_nhw):
+        raise ValueError(f"{op}: out must be [N, Ho, Wo, ldy] = {tuple(out_nhw)} + (ldy,), "
+                         f"got {tuple(out.shape)}")
+    if C <= 0 or x_coff < 0 or y_coff < 0 or any(v % 8 for v in (C, ldx, x_coff, ldy, y_coff)):
+        raise ValueError(f"{op}: C, ldx, x_coff, ldy, y_coff must be multiples of 8, got "
+                         f"{(C, ldx, x_coff, ldy, y_coff)}")
+    if x_coff + C > ldx:
+        raise ValueError(f"{op}: input slice [{x_coff}, {x_coff + C}) exceeds ldx = {ldx}")
+    if y_coff + C > ldy:
+        raise ValueError(f"{op}: output slice [{y_coff}, {y_coff + C}) exceeds ldy = {ldy}")
+
+
 def maxpool2d(x: torch.Tensor, k: int, stride: int, pad: int, out: Optional[torch.Tensor] = None,
               C: Optional[int] = None, x_coff: int = 0, y_coff: int = 0) -> torch.Tensor:
     N, H, W, ldx = x.shape
@@ -573,6 +590,7 @@ def maxpool2d(x: torch.Tensor, k: int, stride: int, pad: int, out: Optional[torc
     Wo = (W + 2 * pad - k) // stride + 1
     if out is None:
         out = empty(N, Ho, Wo, C, dtype=x.dtype, device=x.device)
+    _check_slices("maxpool2d", C, ldx, x_coff, out, y_coff, (N, Ho, Wo))
     if x.is_cuda:
         _native().maxpool2d(x, out, N, H, W, C, ldx, x_coff, out.shape[3], y_coff, k, stride, pad,
                             Ho, Wo)
@@ -644,6 +662,7 @@ def upsample2x(x: torch.Tensor, out: torch.Tensor, C: Optional[int] = None, x_co
                y_coff: int = 0):
     N, H, W, ldx = x.shape
     C = C or (ldx - x_coff)
+    _check_slices("upsample2x", C, ldx, x_coff, out, y_coff, (N, 2 * H, 2 * W))
     if x.is_cuda:
         _native().upsample2x(x, out, N, H, W, C, ldx, x_coff, out.shape[3], y_coff)
     else:
