@@ -846,6 +846,62 @@ void track_update(const at::Tensor& det, const at::Tensor& count, at::Tensor& st
   TORCH_CHECK(rc == 0, "kvedge: track_update failed rc=", rc);
 }
 
+// K19: line crossings and zone occupancy (csrc/kernels/zones.hip), after the same step's
+// track_update.  track_state int32 [S, 12 T + 4] (read only), zone_state int32 [S, 4 T + 48],
+// table int32 [S, 188]; batch row n of det / count is stream slot0 + n
+void zone_update(const at::Tensor& det, const at::Tensor& count, const at::Tensor& track_state,
+                 at::Tensor& zone_state, const at::Tensor& table, at::Tensor& zone_mask,
+                 at::Tensor& zone_counts, int64_t slot0) {
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(track_state, "track_state");
+  check_dev(zone_state, "zone_state");
+  check_dev(table, "table");
+  check_dev(zone_mask, "zone_mask");
+  check_dev(zone_counts, "zone_counts");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6,
+              "kvedge: det fp32 [N,max_det,6]");
+  const int64_t N = det.size(0), max_det = det.size(1);
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == N,
+              "kvedge: count int32 [N]");
+  TORCH_CHECK(track_state.scalar_type() == at::kInt && track_state.dim() == 2 &&
+                  track_state.size(1) >= 4 && (track_state.size(1) - 4) % 12 == 0,
+              "kvedge: track state int32 [S, 12*T+4]");
+  const int64_t S = track_state.size(0), T = (track_state.size(1) - 4) / 12;
+  TORCH_CHECK(T == 64 || T == 128 || T == 192 || T == 256,
+              "kvedge: zone_update max_tracks is 64, 128, 192 or 256, got ", T);
+  TORCH_CHECK(track_state.size(1) == kv_track_state_stride((int)T),
+              "kvedge: track state row size");
+  TORCH_CHECK(zone_state.scalar_type() == at::kInt && zone_state.dim() == 2 &&
+                  zone_state.size(0) == S && zone_state.size(1) == kv_zone_state_stride((int)T),
+              "kvedge: zone state int32 [S, 4*T+48] for the track state's S and T");
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 && table.size(0) == S &&
+                  table.size(1) == kv_zone_table_stride(),
+              "kvedge: zone table int32 [S, ", kv_zone_table_stride(), "]");
+  TORCH_CHECK(zone_mask.scalar_type() == at::kInt && zone_mask.dim() == 2 &&
+                  zone_mask.size(0) == N && zone_mask.size(1) == max_det,
+              "kvedge: zone_mask int32 [N,max_det]");
+  TORCH_CHECK(zone_counts.scalar_type() == at::kInt && zone_counts.dim() == 2 &&
+                  zone_counts.size(0) == N && zone_counts.size(1) == 48,
+              "kvedge: zone_counts int32 [N,48]");
+  TORCH_CHECK(S < (1ll << 24) && N < (1ll << 24), "kvedge: zone_update too many streams");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: zone_update streams [", slot0, ", ",
+              slot0 + N, ") outside the state's ", S);
+  TORCH_CHECK(max_det >= 1 && max_det <= 300, "kvedge: zone_update max_det is 1..300, got ",
+              max_det);
+  TORCH_CHECK(det.device() == count.device() && det.device() == track_state.device() &&
+                  det.device() == zone_state.device() && det.device() == table.device() &&
+                  det.device() == zone_mask.device() && det.device() == zone_counts.device(),
+              "kvedge: zone_update operands on different devices");
+  const c10::DeviceGuard g(det.device());
+  const int rc = kv_zone_update(det.data_ptr<float>(), count.data_ptr<int>(),
+                                track_state.data_ptr<int>(), zone_state.data_ptr<int>(),
+                                table.data_ptr<int>(), zone_mask.data_ptr<int>(),
+                                zone_counts.data_ptr<int>(), (int)N, (int)S, (int)slot0, (int)T,
+                                (int)max_det, cur_stream(det));
+  TORCH_CHECK(rc == 0, "kvedge: zone_update failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -968,6 +1024,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("roi_crop_nv12_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
   m.def("track_update(Tensor det, Tensor count, Tensor(a!) state, Tensor(b!) track_id, int slot0, "
         "int thr_q, int max_age, int min_hits, bool class_aware) -> ()");
+  m.def("zone_update(Tensor det, Tensor count, Tensor track_state, Tensor(a!) zone_state, "
+        "Tensor table, Tensor(b!) zone_mask, Tensor(c!) zone_counts, int slot0) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1013,6 +1071,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("roi_crop_nv12", roi_crop_nv12);
   m.impl("roi_crop_nv12_band", roi_crop_nv12_band);
   m.impl("track_update", track_update);
+  m.impl("zone_update", zone_update);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

@@ -202,6 +202,23 @@ int kv_track_state_stride(int T);
 int kv_track_update(const float* det, const int* count, int* state, int* track_id, int N, int S,
                     int slot0, int T, int max_det, int thr_q, int max_age, int min_hits,
                     int class_aware, hipStream_t s);
+// K19 (zones.hip): line crossings and zone occupancy of streams [slot0, slot0 + N), one launch
+// after the same step's kv_track_update.  track_state int32 [S, kv_track_state_stride(T)] is
+// only read; zone_state int32 [S, kv_zone_state_stride(T)] (per-slot entries, then 48
+// counters) is updated; table int32 [S, kv_zone_table_stride()] holds every stream's lines and
+// polygon zones (read only); det / count as for K18.  zone_mask int32 [N,max_det] gets each
+// row's zone bits, zone_counts int32 [N,48] the stream's counters after the step (line_fwd[8]
+// line_back[8] zone_enter[8] zone_exit[8] zone_occ[8] zone_dwell[8]), every element written.
+// Integer arithmetic, bit-identical to ops.reference.zone_update; semantics and both layouts
+// are at the top of zones.hip.  The table lives in device memory, so its counts and its
+// anchor mode are range-checked where it is built (ops.ZoneSet) and clamped in the kernel.
+// Returns -1 T not 64/128/192/256, -2 slot0 + N > S, -3 max_det outside 1..300, -7 track or
+// zone state not 16-byte aligned, -8 misaligned table.  N == 0 launches nothing.
+int kv_zone_state_stride(int T);
+int kv_zone_table_stride(void);
+int kv_zone_update(const float* det, const int* count, const int* track_state, int* zone_state,
+                   const int* table, int* zone_mask, int* zone_counts, int N, int S, int slot0,
+                   int T, int max_det, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

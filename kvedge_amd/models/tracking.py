@@ -9,6 +9,9 @@ device memory (ops.TrackState) and is updated by one kernel launch per step
 (ops.track_update, csrc/kernels/track.hip): no host in the loop, so the step stays one
 captured graph -- the state tensors are allocated here, outside the graph's pool, and persist
 across replays.
+
+``KvZoned`` wraps a ``KvTracked`` and counts its tracks against virtual lines and polygon zones
+(ops.zone_update, csrc/kernels/zones.hip): one more launch per step, counters in device memory.
 """
 from __future__ import annotations
 
@@ -74,3 +77,60 @@ class KvTracked:
         else:
             out = self.inner.to_source(self.inner(frames), plan)
         return self._track(tuple(out), slot0)
+
+
+class KvZoned:
+    """A ``KvTracked`` model plus virtual lines and polygon zones: outputs
+    ``(det, count, ..., track_id)`` -> ``(det, count, ..., track_id, zone_mask, zone_counts)``.
+    One more launch per step (ops.zone_update, csrc/kernels/zones.hip) reads the tracker state
+    the step just updated and keeps per-camera counters in device memory (ops.ZoneState): line
+    crossings by direction, zone entries, exits, occupancy and dwell frames.  ``zones``
+    (ops.ZoneSet, one table row per camera) is in the pixel frame the boxes are reported in:
+    frame pixels when the engine has a frame size, model pixels otherwise.  The model takes the
+    set over: ``anchor`` ("bottom" or "centre") is written into it (``zones.set_anchor``),
+    replacing whatever mode the set held, and later ``set_line`` / ``set_zone`` calls on it take
+    effect from the next step."""
+
+    stateful = True
+
+    def __init__(self, inner_tracked: KvTracked, zones: "ops.ZoneSet", anchor="bottom"):
+        if not isinstance(inner_tracked, KvTracked):
+            raise TypeError("KvZoned wraps a KvTracked model")
+        self.inner = inner_tracked
+        self.device = inner_tracked.device
+        self.state = inner_tracked.state  # the tracker's, as the telemetry reads it
+        if zones.streams != self.state.streams or zones.device != self.state.device:
+            raise ValueError(f"zones cover {zones.streams} streams on {zones.device}, the tracker "
+                             f"{self.state.streams} on {self.state.device}")
+        self.zones = zones.set_anchor(anchor)
+        self.zone_state = ops.ZoneState(self.state.streams, self.state.max_tracks, self.device)
+        self.resets = 0  # bumped by reset(): host-side totals start over with the counters
+        self.image_size = inner_tracked.image_size
+
+    def convs(self) -> List:
+        return self.inner.convs()
+
+    def flops_per_image(self, hw: int = 640) -> int:
+        return self.inner.flops_per_image(hw)
+
+    def frame_plan(self, src_hw, image_size: int = 0) -> "ops.ResizePlan":
+        return self.inner.frame_plan(src_hw, image_size)
+
+    def reset(self) -> None:
+        """Forget every track and zero every counter, together."""
+        self.inner.reset()
+        self.zone_state.reset()
+        self.resets += 1
+
+    def _zones(self, out, slot0: int):
+        mask, counts = ops.zone_update(out[0], out[1], self.state, self.zone_state, self.zones,
+                                       slot0=slot0)
+        return (*out, mask, counts)
+
+    def __call__(self, frames_u8: torch.Tensor, slot0: int = 0):
+        return self._zones(self.inner(frames_u8, slot0=slot0), slot0)
+
+    def from_source(self, source_frames: torch.Tensor, frames: torch.Tensor,
+                    plan: "ops.ResizePlan", slot0: int = 0, **fmt):
+        return self._zones(self.inner.from_source(source_frames, frames, plan, slot0=slot0,
+                                                  **fmt), slot0)

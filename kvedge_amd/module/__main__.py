@@ -93,6 +93,16 @@ def main(argv=None):
                     help="consecutive matches before a track gets its id (1..255)")
     ap.add_argument("--track-max-tracks", type=int, default=d.track_max_tracks,
                     help="track slots per camera (64, 128, 192 or 256)")
+    ap.add_argument("--lines-json", default="",
+                    help="--track: virtual lines counted on the device, inline JSON "
+                         "'[{\"name\": ..., \"a\": [x, y], \"b\": [x, y], \"class\"?, "
+                         "\"cameras\"?}]' (at most 8; telemetry gains `lines`)")
+    ap.add_argument("--zones-json", default="",
+                    help="--track: polygon zones, inline JSON '[{\"name\": ..., \"polygon\": "
+                         "[[x, y], ...], \"class\"?, \"cameras\"?}]' (at most 8, 3..8 vertices; "
+                         "telemetry gains `zones`)")
+    ap.add_argument("--zone-anchor", default=d.zone_anchor, choices=["bottom", "centre"],
+                    help="the point of a box tested against lines and zones")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -130,7 +140,8 @@ def main(argv=None):
                        crops_per_image=a.crops_per_image, track=a.track,
                        track_iou=a.track_iou, track_max_age=a.track_max_age,
                        track_min_hits=a.track_min_hits,
-                       track_max_tracks=a.track_max_tracks).validate()
+                       track_max_tracks=a.track_max_tracks, lines=a.lines_json,
+                       zones=a.zones_json, zone_anchor=a.zone_anchor).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -194,6 +194,7 @@ class ModuleApp:
         self.clock = clock
         self.engine = None
         self.model = None
+        self.zone_totals = None  # module.zones.ZoneTotals once lines / zones are configured
         self.ring = None
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
@@ -394,6 +395,7 @@ class ModuleApp:
         self.engine = None
         self.model = None
         self.sim = None
+        self.zone_totals = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -425,6 +427,12 @@ class ModuleApp:
                 self.model = KvTracked(self.model, cfg.batch, iou=cfg.track_iou,
                                        max_age=cfg.track_max_age, min_hits=cfg.track_min_hits,
                                        max_tracks=cfg.track_max_tracks)
+                if cfg.lines or cfg.zones:
+                    from ..models.tracking import KvZoned
+                    from .zones import build_zone_set
+
+                    self.model = KvZoned(self.model, build_zone_set(cfg, dev),
+                                         anchor=cfg.zone_anchor)
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -435,6 +443,10 @@ class ModuleApp:
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
+        if hasattr(self.model, "zone_state"):  # prepare() left the counters at zero
+            from .zones import ZoneTotals
+
+            self.zone_totals = ZoneTotals(self.model, cfg.lines, cfg.zones)
         if not self.build_phases:
             # cold-start legs (tools/module_cold_start.py): model built -> tiles tuned
             # (or read from the cache) -> warmed -> graph captured
@@ -473,7 +485,7 @@ class ModuleApp:
                 if self.world > 1 else [err])
         err = next((e for e in errs if e), None)
         if err is not None:
-            self.engine = self.model = None
+            self.engine = self.model = self.zone_totals = None
             self.sim = None
             self._stop_camera()
             if previous is None:
@@ -737,6 +749,8 @@ class ModuleApp:
             st = self.model.state  # live tracks, distinct confirmed objects, lost detections
             res["tracks"] = {"active": st.active(), "unique": st.unique(),
                              "dropped": int(st.dropped.sum())}
+        if self.zone_totals is not None:  # line crossings / zone counts, over all cameras
+            res.update(self.zone_totals.update().summed())
         return res
 
     # ---------------------------------------------------------------- handlers
@@ -812,6 +826,11 @@ class ModuleApp:
                              "last_telemetry": self.last_telemetry,
                              "last_error": self.last_error, "rank": self.rank,
                              "world_size": self.world}
+            if name == "zones":  # the telemetry's lines / zones, per camera
+                if self.zone_totals is None:
+                    return 400, {"error": "no lines or zones configured"}
+                return 200, {"cameras": self.zone_totals.update().per_camera(),
+                             "rank": self.rank}
             if name in ("reconfigure", "benchmark"):
                 if self.rank != 0:
                     return 409, {"error": NOT_CONTROL_POINT.format(rank=self.rank)}

@@ -8,12 +8,59 @@ CLI flags for bare-metal runs (kvedge_amd.module.__main__).
 """
 from __future__ import annotations
 
+import json
 from dataclasses import asdict, dataclass, fields, replace
-from typing import Any, Dict
+from typing import Any, Dict, Tuple
 
 MODELS = ("resnet50", "yolov8n", "detect-classify", "simulated-temperature")
 SOURCES = ("synthetic", "camera", "camera-nv12")
 DTYPES = ("bf16",)
+ZONE_ANCHORS = ("bottom", "centre")
+MAX_REGIONS = 8  # lines, and zones, per camera (csrc/kernels/zones.hip)
+
+
+def _point(p, what: str):
+    if not isinstance(p, (list, tuple)) or len(p) != 2:
+        raise ValueError(f"{what} must be [x, y], got {p!r}")
+    return [float(p[0]), float(p[1])]
+
+
+def _regions(v, kind: str) -> Tuple[Dict[str, Any], ...]:
+    """The ``lines`` / ``zones`` twin key (a list of objects, or the same as a JSON string) in
+    normal form: name, class (-1 = any), cameras (None = all) and the geometry as floats."""
+    if isinstance(v, str):
+        v = json.loads(v) if v.strip() else []
+    if v is None:
+        v = []
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"{kind} must be a list, got {type(v).__name__}")
+    out = []
+    for i, r in enumerate(v):
+        if not isinstance(r, dict):
+            raise ValueError(f"{kind}[{i}] must be an object, got {r!r}")
+        unknown = set(r) - ({"name", "class", "cameras"} |
+                            ({"a", "b"} if kind == "lines" else {"polygon"}))
+        if unknown:
+            raise ValueError(f"{kind}[{i}]: unknown keys {sorted(unknown)}")
+        name = str(r.get("name", ""))
+        if not name:
+            raise ValueError(f"{kind}[{i}] needs a name")
+        cams = r.get("cameras")
+        if cams is not None:
+            if not isinstance(cams, (list, tuple)):
+                raise ValueError(f"{kind}[{i}].cameras must be a list of camera indices")
+            cams = [int(c) for c in cams]
+        n = {"name": name, "class": int(r.get("class", -1)), "cameras": cams}
+        if kind == "lines":
+            n["a"] = _point(r.get("a"), f"{kind}[{i}].a")
+            n["b"] = _point(r.get("b"), f"{kind}[{i}].b")
+        else:
+            poly = r.get("polygon")
+            if not isinstance(poly, (list, tuple)):
+                raise ValueError(f"{kind}[{i}].polygon must be a list of [x, y]")
+            n["polygon"] = [_point(p, f"{kind}[{i}].polygon[{j}]") for j, p in enumerate(poly)]
+        out.append(n)
+    return tuple(out)
 
 
 @dataclass(frozen=True)
@@ -57,6 +104,15 @@ class ModuleConfig:
     track_max_age: int = 30
     track_min_hits: int = 3
     track_max_tracks: int = 64
+    # virtual lines and polygon zones on the tracked boxes (they need `track`), counted on the
+    # device (ops.zone_update): up to 8 of each per camera, in the pixel frame the boxes are
+    # reported in.  lines: [{name, a: [x, y], b: [x, y], class?, cameras?}]; zones: [{name,
+    # polygon: [[x, y], ...] (3..8 vertices), class?, cameras?}]; class: only that class counts
+    # (default -1, any); cameras: batch rows the region applies to (default all).
+    # zone_anchor: the point of a box that is tested, "bottom" (bottom-centre) or "centre"
+    lines: Tuple[Dict[str, Any], ...] = ()
+    zones: Tuple[Dict[str, Any], ...] = ()
+    zone_anchor: str = "bottom"
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -76,7 +132,12 @@ class ModuleConfig:
     # keys that force an engine rebuild when they change
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
                "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
-               "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
+               "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
+               "lines", "zones", "zone_anchor")
+
+    def __post_init__(self):
+        for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
+            object.__setattr__(self, kind, _regions(getattr(self, kind), kind))
 
     def validate(self) -> "ModuleConfig":
         if self.model not in MODELS:
@@ -128,6 +189,25 @@ class ModuleConfig:
             raise ValueError("track_max_tracks must be 64, 128, 192 or 256")
         if self.track and self.model not in ("yolov8n", "detect-classify"):  # binds only when on
             raise ValueError("track needs a detector: model yolov8n or detect-classify")
+        if self.zone_anchor not in ZONE_ANCHORS:
+            raise ValueError(f"zone_anchor must be one of {ZONE_ANCHORS}, got {self.zone_anchor!r}")
+        for kind in ("lines", "zones"):
+            regions = getattr(self, kind)
+            if len(regions) > MAX_REGIONS:
+                raise ValueError(f"at most {MAX_REGIONS} {kind}, got {len(regions)}")
+            names = [r["name"] for r in regions]
+            if len(set(names)) != len(names):
+                raise ValueError(f"{kind} names must be unique, got {names}")
+            for r in regions:
+                if not -1 <= r["class"] <= 65535:
+                    raise ValueError(f"{kind} {r['name']!r}: class must be -1..65535")
+                if r["cameras"] is not None and not all(0 <= c < self.batch for c in r["cameras"]):
+                    raise ValueError(f"{kind} {r['name']!r}: cameras must be 0..batch - 1")
+                if kind == "zones" and not 3 <= len(r["polygon"]) <= 8:
+                    raise ValueError(f"zone {r['name']!r} needs 3..8 vertices, got "
+                                     f"{len(r['polygon'])}")
+        if (self.lines or self.zones) and not self.track:
+            raise ValueError("lines / zones count tracked objects: they need track true")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -151,6 +231,8 @@ class ModuleConfig:
                 v = int(v)
             elif isinstance(cur, float):
                 v = float(v)
+            elif isinstance(cur, tuple):
+                v = _regions(v, k)
             else:
                 v = str(v)
             kw[k] = v
@@ -177,6 +259,7 @@ class ModuleConfig:
         return "nv12" if self.source == "camera-nv12" else "rgb"
 
     TRACK_KEYS = ("track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
+    ZONE_KEYS = ("lines", "zones", "zone_anchor")
 
     def to_dict(self) -> Dict[str, Any]:
         """The reported / saved config.  The tracking keys are listed once any of them has
@@ -187,4 +270,10 @@ class ModuleConfig:
         if all(getattr(self, k) == getattr(base, k) for k in self.TRACK_KEYS):
             for k in self.TRACK_KEYS:
                 d.pop(k)
+        # likewise the line / zone keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.ZONE_KEYS):
+            for k in self.ZONE_KEYS:
+                d.pop(k)
+        else:
+            d["lines"], d["zones"] = list(d["lines"]), list(d["zones"])
         return d

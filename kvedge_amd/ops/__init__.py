@@ -1044,6 +1044,215 @@ def track_update(det: torch.Tensor, count: torch.Tensor, state: TrackState, slot
     return out
 
 
+# ---------------------------------------------------------------------------
+# lines and zones: stable ids -> crossings, occupancy, dwell
+# ---------------------------------------------------------------------------
+ZONE_MAX_LINES = 8
+ZONE_MAX_ZONES = 8
+ZONE_MAX_VERTICES = 8
+ZONE_COUNTERS = ("line_fwd", "line_back", "zone_enter", "zone_exit", "zone_occ", "zone_dwell")
+ZONE_TABLE_STRIDE = 188
+ZONE_ANCHORS = {"bottom": 0, "centre": 1, "center": 1, 0: 0, 1: 1}
+
+
+def _zone_q(xy) -> list:
+    """A pixel point (x, y) -> the tracker's quarter pixels (reference.track_quantize)."""
+    if len(xy) != 2:
+        raise ValueError(f"a point is (x, y), got {xy!r}")
+    return _ref.track_quantize(torch.tensor([float(xy[0]), float(xy[1])])).tolist()
+
+
+class ZoneSet:
+    """The virtual lines and polygon zones of ``streams`` cameras: one int32 table ``table``
+    [streams, 188] on ``device`` (the layout csrc/kernels/zones.hip reads) and named views into
+    it: ``line`` [S, 8, 4] (ax, ay, bx, by), ``line_cls`` [S, 8], ``vertex`` [S, 8, 8, 2],
+    ``n_vertex`` [S, 8], ``zone_cls`` [S, 8] (-1 = any class), ``n_lines`` / ``n_zones`` /
+    ``anchor`` [S].  Coordinates are given in pixels and stored in the tracker's quarter
+    pixels.  An index that was never set holds a line with A == B or a zone without vertices:
+    neither ever counts."""
+
+    def __init__(self, streams: int, device="cpu"):
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        self.streams = int(streams)
+        self._host = torch.zeros(self.streams, ZONE_TABLE_STRIDE, dtype=torch.int32)
+        self.table = self._host if torch.device(device).type == "cpu" else self._host.to(device)
+        for name, v in self._views(self.table).items():
+            setattr(self, name, v)
+        self.clear()
+
+    @staticmethod
+    def _views(tab: torch.Tensor) -> dict:
+        return {"line": tab[:, 0:32].unflatten(1, (8, 4)), "line_cls": tab[:, 32:40],
+                "vertex": tab[:, 40:168].unflatten(1, (8, 8, 2)), "n_vertex": tab[:, 168:176],
+                "zone_cls": tab[:, 176:184], "n_lines": tab[:, 184], "n_zones": tab[:, 185],
+                "anchor": tab[:, 186]}
+
+    @property
+    def device(self) -> torch.device:
+        return self.table.device
+
+    def _push(self) -> None:
+        if self.table is not self._host:
+            self.table.copy_(self._host)
+
+    def _rows(self, camera):
+        if camera is None:
+            return slice(None)
+        if not 0 <= int(camera) < self.streams:
+            raise ValueError(f"camera {camera} outside 0..{self.streams - 1}")
+        return slice(int(camera), int(camera) + 1)
+
+    def clear(self) -> "ZoneSet":
+        """Drop every line and zone (the anchor mode stays)."""
+        anchor = self._host[:, 186].clone()
+        self._host.zero_()
+        h = self._views(self._host)
+        h["line_cls"].fill_(-1)
+        h["zone_cls"].fill_(-1)
+        h["anchor"].copy_(anchor)
+        self._push()
+        return self
+
+    def set_anchor(self, anchor) -> "ZoneSet":
+        """``"bottom"`` (0: bottom-centre of the box, feet on the ground plane) or
+        ``"centre"`` (1)."""
+        if anchor not in ZONE_ANCHORS:
+            raise ValueError(f"anchor must be 'bottom' or 'centre', got {anchor!r}")
+        self._host[:, 186] = ZONE_ANCHORS[anchor]
+        self._push()
+        return self
+
+    def set_line(self, camera, index: int, a, b, cls: int = -1) -> "ZoneSet":
+        """Line ``index`` of ``camera`` (None: of every camera) from pixel point ``a`` to
+        ``b``.  With side(P) = cross(b - a, P - a) >= 0, a move from side true to side false
+        is "forward", the other way "backward".  ``cls``: only tracks of that class count
+        (-1: any)."""
+        if not 0 <= int(index) < ZONE_MAX_LINES:
+            raise ValueError(f"line index {index} outside 0..{ZONE_MAX_LINES - 1}")
+        if not -1 <= int(cls) <= 65535:
+            raise ValueError(f"class {cls} outside -1..65535")
+        rows, h = self._rows(camera), self._views(self._host)
+        h["line"][rows, index] = torch.tensor(_zone_q(a) + _zone_q(b), dtype=torch.int32)
+        h["line_cls"][rows, index] = int(cls)
+        h["n_lines"][rows] = h["n_lines"][rows].clamp_min(int(index) + 1)
+        self._push()
+        return self
+
+    def set_zone(self, camera, index: int, polygon, cls: int = -1) -> "ZoneSet":
+        """Zone ``index`` of ``camera`` (None: of every camera): a polygon of 3..8 pixel
+        vertices, convex or not.  ``cls``: only that class counts (-1: any)."""
+        if not 0 <= int(index) < ZONE_MAX_ZONES:
+            raise ValueError(f"zone index {index} outside 0..{ZONE_MAX_ZONES - 1}")
+        polygon = list(polygon)
+        if not 3 <= len(polygon) <= ZONE_MAX_VERTICES:
+            raise ValueError(f"a zone has 3..{ZONE_MAX_VERTICES} vertices, got {len(polygon)}")
+        if not -1 <= int(cls) <= 65535:
+            raise ValueError(f"class {cls} outside -1..65535")
+        rows, h = self._rows(camera), self._views(self._host)
+        v = torch.zeros(ZONE_MAX_VERTICES, 2, dtype=torch.int32)
+        v[:len(polygon)] = torch.tensor([_zone_q(p) for p in polygon], dtype=torch.int32)
+        h["vertex"][rows, index] = v
+        h["n_vertex"][rows, index] = len(polygon)
+        h["zone_cls"][rows, index] = int(cls)
+        h["n_zones"][rows] = h["n_zones"][rows].clamp_min(int(index) + 1)
+        self._push()
+        return self
+
+
+class ZoneState:
+    """Line / zone state of ``streams`` cameras over a tracker of ``max_tracks`` slots: one
+    int32 buffer ``buf`` [streams, 4 * max_tracks + 48] (the layout csrc/kernels/zones.hip
+    reads) and named views: ``entry`` [S, T, 4] = ``seen_id`` (-1 = none), ``anchor`` [S, T, 2]
+    (quarter pixels at the last sighting), ``zmask``; ``counters`` [S, 48] = ``line_fwd``
+    ``line_back`` ``zone_enter`` ``zone_exit`` ``zone_occ`` ``zone_dwell`` [S, 8] each,
+    cumulative and wrapping modulo 2^32 (``zone_occ``: the current value)."""
+
+    def __init__(self, streams: int, max_tracks: int = 64, device="cpu"):
+        if max_tracks not in TRACK_MAX_TRACKS:
+            raise ValueError(f"max_tracks must be one of {TRACK_MAX_TRACKS}, got {max_tracks}")
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+        T = self.max_tracks
+        self.buf = torch.zeros(self.streams, 4 * T + 48, dtype=torch.int32, device=device)
+        self.entry = self.buf[:, :4 * T].unflatten(1, (T, 4))
+        self.seen_id = self.entry[..., 0]
+        self.anchor = self.entry[..., 1:3]
+        self.zmask = self.entry[..., 3]
+        self.counters = self.buf[:, 4 * T:]
+        for i, name in enumerate(ZONE_COUNTERS):
+            setattr(self, name, self.counters[:, 8 * i:8 * i + 8])
+        self.reset()
+
+    @property
+    def device(self) -> torch.device:
+        return self.buf.device
+
+    def reset(self) -> "ZoneState":
+        """Forget every entry and zero the counters (device ops on the current stream)."""
+        self.buf.zero_()
+        self.seen_id.fill_(-1)
+        return self
+
+
+def zone_update(det: torch.Tensor, count: torch.Tensor, track_state: TrackState,
+                zone_state: ZoneState, zones: ZoneSet, slot0: int = 0,
+                out_mask: Optional[torch.Tensor] = None,
+                out_counts: Optional[torch.Tensor] = None):
+    """One line / zone step, after the same step's :func:`track_update` on the same ``det`` /
+    ``count`` / ``track_state`` (which is only read).  Updates the counters of streams
+    [slot0, slot0 + N) in ``zone_state`` -- line crossings by direction, zone entries, exits,
+    occupancy, dwell frames -- and returns ``(zone_mask, zone_counts)``: int32 [N, max_det],
+    bit z set when the anchor of the row's box lies in zone z (rows >= count[n]: 0), and int32
+    [N, 48], the stream's counters after the step in the order of ``ZONE_COUNTERS``.  Integer
+    arithmetic on quarter pixels: GPU (csrc/kernels/zones.hip) and CPU
+    (ops.reference.zone_update, where the rules are written out) are bit-identical."""
+    if not isinstance(track_state, TrackState):
+        raise TypeError(f"track_state must be an ops.TrackState, got {type(track_state).__name__}")
+    if not isinstance(zone_state, ZoneState):
+        raise TypeError(f"zone_state must be an ops.ZoneState, got {type(zone_state).__name__}")
+    if not isinstance(zones, ZoneSet):
+        raise TypeError(f"zones must be an ops.ZoneSet, got {type(zones).__name__}")
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6:
+        raise ValueError(f"det must be fp32 [N, max_det, 6], got {det.dtype} {tuple(det.shape)}")
+    n, max_det = int(det.shape[0]), int(det.shape[1])
+    if count.dtype != torch.int32 or tuple(count.shape) != (n,):
+        raise ValueError(f"count must be int32 [{n}], got {count.dtype} {tuple(count.shape)}")
+    if not det.is_contiguous() or not count.is_contiguous():
+        raise ValueError("det and count must be contiguous")
+    for name, dev in (("count", count.device), ("track_state", track_state.device),
+                      ("zone_state", zone_state.device), ("zones", zones.device)):
+        if dev != det.device:
+            raise ValueError(f"det on {det.device}, {name} on {dev}")
+    if not 1 <= max_det <= TRACK_MAX_DET:
+        raise ValueError(f"zone_update needs 1 <= max_det <= {TRACK_MAX_DET}, got {max_det}")
+    if (zone_state.streams, zone_state.max_tracks) != (track_state.streams,
+                                                       track_state.max_tracks):
+        raise ValueError("zone_state and track_state differ in streams or max_tracks")
+    if zones.streams != track_state.streams:
+        raise ValueError(f"zones cover {zones.streams} streams, the state {track_state.streams}")
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > track_state.streams:
+        raise ValueError(f"streams [{slot0}, {slot0 + n}) outside the state's "
+                         f"{track_state.streams}")
+    if out_mask is None:
+        out_mask = empty(n, max_det, dtype=torch.int32, device=det.device)
+    if out_counts is None:
+        out_counts = empty(n, 48, dtype=torch.int32, device=det.device)
+    for name, t, shape in (("out_mask", out_mask, (n, max_det)),
+                           ("out_counts", out_counts, (n, 48))):
+        if (t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != det.device):
+            raise ValueError(f"{name} must be contiguous int32 {list(shape)} on {det.device}")
+    if det.is_cuda:
+        _native().zone_update(det, count, track_state.buf, zone_state.buf, zones.table, out_mask,
+                              out_counts, slot0)
+    else:
+        _ref.zone_update(det, count, track_state, zone_state, zones, slot0, out_mask, out_counts)
+    return out_mask, out_counts
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -376,6 +376,157 @@ def track_update(det, count, state, slot0, thr_q, max_age, min_hits, class_aware
     return out
 
 
+ZONE_MAX = 8  # lines, zones and vertices per zone, per camera
+
+
+def zone_anchor(box, centre):
+    """Anchor of quarter-pixel boxes int64 [..., 4]: bottom-centre ((x1 + x2) >> 1, y2), or the
+    centre ((x1 + x2) >> 1, (y1 + y2) >> 1).  Returns (px, py)."""
+    px = (box[..., 0] + box[..., 2]) >> 1
+    py = (box[..., 1] + box[..., 3]) >> 1 if centre else box[..., 3]
+    return px, py
+
+
+def point_in_polygon(px, py, poly):
+    """Crossing number in integers: px, py int64 tensors (any shape), poly a list of (x, y)
+    ints.  The edge (xi, yi) -> (xj, yj) toggles a point when (yi > py) != (yj > py) and px is
+    strictly left of it: t = (xj - xi) (py - yi) - (px - xi) (yj - yi) has the sign of
+    yj - yi.  No divide; points on an edge fall wherever this puts them."""
+    inside = torch.zeros_like(px, dtype=torch.bool)
+    xj, yj = poly[-1]
+    for xi, yi in poly:
+        dy = yj - yi
+        t = (xj - xi) * (py - yi) - (px - xi) * dy
+        left = (t > 0) if dy > 0 else (t < 0)
+        inside ^= ((yi > py) != (yj > py)) & left
+        xj, yj = xi, yi
+    return inside
+
+
+def _zone_masks(px, py, cls, tab):
+    """Bit z: zone z of the table row holds (px, py) and its class filter passes cls."""
+    m = torch.zeros_like(px)
+    n_zones = min(max(int(tab["n_zones"]), 0), ZONE_MAX)
+    for z in range(n_zones):
+        nv = min(max(int(tab["n_vertex"][z]), 0), ZONE_MAX)
+        if nv < 3:
+            continue
+        poly = [(int(x), int(y)) for x, y in tab["vertex"][z, :nv].tolist()]
+        zc = int(tab["zone_cls"][z])
+        hit = point_in_polygon(px, py, poly)
+        if zc != -1:
+            hit &= cls == zc
+        m |= hit.long() << z
+    return m
+
+
+def _cross(ux, uy, vx, vy):
+    return ux * vy - uy * vx
+
+
+def line_crossing(p0, p1, a, b):
+    """The move p0 -> p1 over the segment a -> b, all (x, y) ints: +1 forward, -1 backward,
+    0 none.  side(P) = cross(b - a, P - a) >= 0 and sp(X) = cross(p1 - p0, X - p0) >= 0; a
+    crossing needs side(p0) != side(p1) and sp(a) != sp(b).  Both half-open: a path through the
+    end point two chained segments share counts on exactly one of them.  a == b: side() is
+    true everywhere, never a crossing."""
+    s0 = _cross(b[0] - a[0], b[1] - a[1], p0[0] - a[0], p0[1] - a[1]) >= 0
+    s1 = _cross(b[0] - a[0], b[1] - a[1], p1[0] - a[0], p1[1] - a[1]) >= 0
+    pa = _cross(p1[0] - p0[0], p1[1] - p0[1], a[0] - p0[0], a[1] - p0[1]) >= 0
+    pb = _cross(p1[0] - p0[0], p1[1] - p0[1], b[0] - p0[0], b[1] - p0[1]) >= 0
+    if s0 == s1 or pa == pb:
+        return 0
+    return 1 if s0 else -1
+
+
+def _wrap32(v):
+    return ((int(v) + (1 << 31)) % (1 << 32)) - (1 << 31)
+
+
+def zone_update(det, count, track_state, zone_state, zones, slot0, out_mask, out_counts):
+    """Line crossings and zone occupancy after the same step's track_update: THE definition the
+    HIP kernel (csrc/kernels/zones.hip) equals bit for bit.  ``track_state`` (ops.TrackState) is
+    only read; ``zone_state`` (ops.ZoneState) and the outputs are written; ``zones``
+    (ops.ZoneSet) is the region table; all on the CPU.  Row n is stream ``slot0 + n``.
+
+    The table's n_lines, n_zones and vertex counts are clamped to 0..8 (fewer than 3 vertices:
+    an empty zone), anchor 1 is the centre and anything else bottom-centre.  Per slot t, with
+    cur = id if hits > 0 and id >= 0 else -1 and the entry (seen_id, ax, ay, zmask):
+
+    1. seen_id != cur and seen_id >= 0 (track gone, or slot reused): zone_exit[z] += 1 for
+       every bit of zmask; the entry is cleared to (-1, 0, 0, 0);
+    2. cur >= 0 and age == 0 (seen this frame): P1 = anchor(box), m1 = the zones holding P1
+       whose class filter passes cls.  seen_id == cur: every class-passing line is tested with
+       P0 = (ax, ay) -> line_fwd / line_back; zone_enter gets m1 & ~zmask, zone_exit gets
+       zmask & ~m1.  Otherwise (first sighting): zone_enter gets m1, no line test.
+       The entry becomes (cur, P1, m1);
+    3. coasting tracks (age > 0) keep their entry;
+    4. zone_occ[z] = entries with seen_id >= 0 and bit z; zone_dwell[z] += zone_occ[z].
+
+    Counters are int32 and wrap modulo 2^32.  out_mask [N, max_det]: zones holding the anchor of
+    each row r < count[n] (the row's own quantised box and class), 0 elsewhere; out_counts
+    [N, 48]: line_fwd line_back zone_enter zone_exit zone_occ zone_dwell after the step."""
+    N, max_det, _ = det.shape
+    for n in range(N):
+        s = slot0 + n
+        tab = {k: getattr(zones, k)[s] for k in
+               ("line", "line_cls", "vertex", "n_vertex", "zone_cls", "n_lines", "n_zones",
+                "anchor")}
+        centre = int(tab["anchor"]) == 1
+        n_lines = min(max(int(tab["n_lines"]), 0), ZONE_MAX)
+        box, cls = track_state.box[s].long(), track_state.cls[s].long()
+        tid, age, hits = track_state.id[s], track_state.age[s], track_state.hits[s]
+        px, py = zone_anchor(box, centre)
+        m_slot = _zone_masks(px, py, cls, tab)
+        delta = [0] * 32  # line_fwd, line_back, zone_enter, zone_exit
+        tid, age, hits, cls_l = tid.tolist(), age.tolist(), hits.tolist(), cls.tolist()
+        px_l, py_l, m_slot = px.tolist(), py.tolist(), m_slot.tolist()
+        lines = [(tab["line"][ln].tolist(), int(tab["line_cls"][ln])) for ln in range(n_lines)]
+        entry = zone_state.entry[s].tolist()
+        for t in range(len(entry)):
+            cur = tid[t] if hits[t] > 0 and tid[t] >= 0 else -1
+            seen, ax, ay, zmask = entry[t]
+            if seen != cur and seen >= 0:
+                for z in range(ZONE_MAX):
+                    delta[24 + z] += (zmask >> z) & 1
+                seen, ax, ay, zmask = -1, 0, 0, 0
+            if cur >= 0 and age[t] == 0:
+                p1, m1 = (px_l[t], py_l[t]), m_slot[t]
+                if seen == cur:
+                    for ln, ((x0, y0, x1, y1), lc) in enumerate(lines):
+                        if lc != -1 and lc != cls_l[t]:
+                            continue
+                        c = line_crossing((ax, ay), p1, (x0, y0), (x1, y1))
+                        if c:
+                            delta[ln if c > 0 else 8 + ln] += 1
+                    enter, leave = m1 & ~zmask, zmask & ~m1
+                else:
+                    enter, leave = m1, 0
+                for z in range(ZONE_MAX):
+                    delta[16 + z] += (enter >> z) & 1
+                    delta[24 + z] += (leave >> z) & 1
+                seen, ax, ay, zmask = cur, p1[0], p1[1], m1
+            entry[t] = [seen, ax, ay, zmask]
+        zone_state.entry[s] = torch.tensor(entry, dtype=torch.int32)
+        ctr = zone_state.counters[s]
+        for i in range(32):
+            ctr[i] = _wrap32(int(ctr[i]) + delta[i])
+        live = zone_state.seen_id[s] >= 0
+        for z in range(ZONE_MAX):
+            occ = int((live & (((zone_state.zmask[s] >> z) & 1) == 1)).sum())
+            ctr[32 + z] = occ
+            ctr[40 + z] = _wrap32(int(ctr[40 + z]) + occ)
+        out_counts[n] = ctr
+        cnt = min(max(int(count[n]), 0), max_det)
+        out_mask[n] = 0
+        if cnt:
+            dq = track_quantize(det[n, :cnt, :4])
+            rx, ry = zone_anchor(dq, centre)
+            out_mask[n, :cnt] = _zone_masks(rx, ry, track_class(det[n, :cnt, 5]), tab).to(
+                torch.int32)
+    return out_mask, out_counts
+
+
 def conv_dual2(x, x_coff, K1, x2, x2_coff, w, bias, act, stride2, up2, out, y_coff):
     K2 = w.shape[1] - K1
     a = x[..., x_coff:x_coff + K1].float()
