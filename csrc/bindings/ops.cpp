@@ -902,6 +902,62 @@ void zone_update(const at::Tensor& det, const at::Tensor& count, const at::Tenso
   TORCH_CHECK(rc == 0, "kvedge: zone_update failed rc=", rc);
 }
 
+// K20: per-camera frame watch (csrc/kernels/frame_watch.hip).  src uint8 RGB [N,Hs,Ws,3] or
+// NV12 [N,Hs*3/2,Ws]; state int32 [S, 24 + 3 GH GW]; batch row n of src is stream slot0 + n.
+// Everything is validated before the first launch: a rejected call leaves state, stats and
+// mask untouched.
+void frame_watch(const at::Tensor& src, at::Tensor& state, at::Tensor& stats, at::Tensor& mask,
+                 int64_t slot0, bool nv12, int64_t cell, int64_t row_step, int64_t bg_shift) {
+  check_dev(src, "src");
+  check_dev(state, "state");
+  check_dev(stats, "stats");
+  check_dev(mask, "mask");
+  TORCH_CHECK(src.scalar_type() == at::kByte, "kvedge: frame_watch src must be uint8");
+  int64_t N, Hs, Ws;
+  if (nv12) {
+    TORCH_CHECK(src.dim() == 3, "kvedge: frame_watch NV12 src uint8 [N,Hs*3/2,Ws]");
+    N = src.size(0);
+    Ws = src.size(2);
+    Hs = src.size(1) * 2 / 3;
+    TORCH_CHECK(Hs % 2 == 0 && Ws % 2 == 0 && src.size(1) == Hs * 3 / 2,
+                "kvedge: frame_watch NV12 needs an even frame height and width, got rows=",
+                src.size(1), " Ws=", Ws);
+  } else {
+    TORCH_CHECK(src.dim() == 4 && src.size(3) == 3, "kvedge: frame_watch RGB src uint8 [N,Hs,Ws,3]");
+    N = src.size(0);
+    Hs = src.size(1);
+    Ws = src.size(2);
+  }
+  TORCH_CHECK(Hs >= 1 && Hs <= 4096 && Ws >= 2 && Ws <= 4096,
+              "kvedge: frame_watch frame size 1..4096 x 2..4096, got ", Hs, "x", Ws);
+  TORCH_CHECK(cell == 8 || cell == 16 || cell == 32, "kvedge: frame_watch cell is 8, 16 or 32");
+  TORCH_CHECK(row_step == 1 || row_step == 2 || row_step == 4,
+              "kvedge: frame_watch row_step is 1, 2 or 4");
+  TORCH_CHECK(bg_shift >= 0 && bg_shift <= 8, "kvedge: frame_watch bg_shift is 0..8");
+  const int64_t GH = (Hs + cell - 1) / cell, GW = (Ws + cell - 1) / cell;
+  TORCH_CHECK(state.scalar_type() == at::kInt && state.dim() == 2 &&
+                  state.size(1) == kv_watch_state_stride((int)(GH * GW)),
+              "kvedge: watch state int32 [S, 24+3*GH*GW] for the frame size and cell");
+  const int64_t S = state.size(0);
+  TORCH_CHECK(stats.scalar_type() == at::kInt && stats.dim() == 2 && stats.size(0) == N &&
+                  stats.size(1) == 16, "kvedge: frame_watch stats int32 [N,16]");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.dim() == 3 && mask.size(0) == N &&
+                  mask.size(1) == GH && mask.size(2) == GW,
+              "kvedge: frame_watch motion_mask uint8 [N,GH,GW]");
+  TORCH_CHECK(S < (1ll << 24) && N <= 65535, "kvedge: frame_watch too many streams");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: frame_watch streams [", slot0, ", ",
+              slot0 + N, ") outside the state's ", S);
+  TORCH_CHECK(src.device() == state.device() && src.device() == stats.device() &&
+                  src.device() == mask.device(),
+              "kvedge: frame_watch operands on different devices");
+  const c10::DeviceGuard g(src.device());
+  const int rc = kv_frame_watch(src.data_ptr<uint8_t>(), state.data_ptr<int>(),
+                                stats.data_ptr<int>(), mask.data_ptr<uint8_t>(), (int)N, (int)S,
+                                (int)slot0, (int)Hs, (int)Ws, nv12 ? 1 : 0, (int)cell,
+                                (int)row_step, (int)bg_shift, cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: frame_watch failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -1026,6 +1082,8 @@ TORCH_LIBRARY(kvedge, m) {
         "int thr_q, int max_age, int min_hits, bool class_aware) -> ()");
   m.def("zone_update(Tensor det, Tensor count, Tensor track_state, Tensor(a!) zone_state, "
         "Tensor table, Tensor(b!) zone_mask, Tensor(c!) zone_counts, int slot0) -> ()");
+  m.def("frame_watch(Tensor src, Tensor(a!) state, Tensor(b!) stats, Tensor(c!) mask, int slot0, "
+        "bool nv12, int cell, int row_step, int bg_shift) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1072,6 +1130,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("roi_crop_nv12_band", roi_crop_nv12_band);
   m.impl("track_update", track_update);
   m.impl("zone_update", zone_update);
+  m.impl("frame_watch", frame_watch);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

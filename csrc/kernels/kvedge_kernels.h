@@ -219,6 +219,21 @@ int kv_zone_table_stride(void);
 int kv_zone_update(const float* det, const int* count, const int* track_state, int* zone_state,
                    const int* table, int* zone_mask, int* zone_counts, int N, int S, int slot0,
                    int T, int max_det, hipStream_t s);
+// K20 (frame_watch.hip): per-camera frame watch of streams [slot0, slot0 + N): a motion grid
+// against a running background, and the dark / flat / frozen / scene conditions with their run
+// counters and alarms.  src uint8: RGB [N,Hs,Ws,3] (nv12 == 0) or NV12 [N,Hs*3/2,Ws] (luma only
+// is read); state int32 [S, kv_watch_state_stride(GH * GW)], GH = ceil(Hs / cell), GW =
+// ceil(Ws / cell), holds the header (primed, run[5], raised[5], the six thresholds, which are
+// clamped in the kernel) and the per-cell planes acc | sum | grad.  stats int32 [N,16] and mask
+// uint8 [N,GH,GW]: every element written.  Integer arithmetic, bit-identical to
+// ops.reference.frame_watch; the rules and the layout are at the top of frame_watch.hip.
+// Returns -1 Hs outside 1..4096 or Ws outside 2..4096, -2 slot0 + N > S, -3 cell not 8/16/32,
+// -4 row_step not 1/2/4, -5 bg_shift outside 0..8, -6 odd NV12 size, -7 misaligned state or
+// stats, -9 N too large.  N == 0 launches nothing.
+int kv_watch_state_stride(int cells);
+int kv_frame_watch(const unsigned char* src, int* state, int* stats, unsigned char* mask, int N,
+                   int S, int slot0, int Hs, int Ws, int nv12, int cell, int row_step,
+                   int bg_shift, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

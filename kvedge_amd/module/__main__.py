@@ -103,6 +103,28 @@ def main(argv=None):
                          "telemetry gains `zones`)")
     ap.add_argument("--zone-anchor", default=d.zone_anchor, choices=["bottom", "centre"],
                     help="the point of a box tested against lines and zones")
+    ap.add_argument("--watch", action="store_true",
+                    help="watch every camera's frames on the device (one batch row = one "
+                         "camera): motion grid, dark / flat / frozen / scene alarms; telemetry "
+                         "gains `cameras` and `camera_alarms`")
+    ap.add_argument("--watch-cell", type=int, default=d.watch_cell, choices=[8, 16, 32],
+                    help="motion grid cell, pixels")
+    ap.add_argument("--watch-row-step", type=int, default=d.watch_row_step, choices=[1, 2, 4],
+                    help="read every n-th frame row")
+    ap.add_argument("--watch-bg-shift", type=int, default=d.watch_bg_shift,
+                    help="background = mean of about 2^k frames (0..8; 0 = frame differencing)")
+    ap.add_argument("--watch-motion-level", type=float, default=d.watch_motion_level,
+                    help="luma levels a cell must differ from the background to move")
+    ap.add_argument("--watch-motion-share", type=float, default=d.watch_motion_share,
+                    help="share of moving cells for `motion`")
+    ap.add_argument("--watch-scene-share", type=float, default=d.watch_scene_share,
+                    help="share of moving cells for `scene` (camera moved or covered)")
+    ap.add_argument("--watch-dark-level", type=float, default=d.watch_dark_level,
+                    help="mean luma below which the scene is `dark`")
+    ap.add_argument("--watch-flat-level", type=float, default=d.watch_flat_level,
+                    help="mean neighbour difference below which the picture is `flat`")
+    ap.add_argument("--watch-hold", type=int, default=d.watch_hold,
+                    help="frames a condition must hold before its alarm (1..255)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -141,7 +163,14 @@ def main(argv=None):
                        track_iou=a.track_iou, track_max_age=a.track_max_age,
                        track_min_hits=a.track_min_hits,
                        track_max_tracks=a.track_max_tracks, lines=a.lines_json,
-                       zones=a.zones_json, zone_anchor=a.zone_anchor).validate()
+                       zones=a.zones_json, zone_anchor=a.zone_anchor, watch=a.watch,
+                       watch_cell=a.watch_cell, watch_row_step=a.watch_row_step,
+                       watch_bg_shift=a.watch_bg_shift,
+                       watch_motion_level=a.watch_motion_level,
+                       watch_motion_share=a.watch_motion_share,
+                       watch_scene_share=a.watch_scene_share,
+                       watch_dark_level=a.watch_dark_level,
+                       watch_flat_level=a.watch_flat_level, watch_hold=a.watch_hold).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

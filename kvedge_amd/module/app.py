@@ -195,6 +195,7 @@ class ModuleApp:
         self.engine = None
         self.model = None
         self.zone_totals = None  # module.zones.ZoneTotals once lines / zones are configured
+        self.camera_totals = None  # module.watch.CameraTotals with `watch` on
         self.ring = None
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
@@ -396,6 +397,7 @@ class ModuleApp:
         self.model = None
         self.sim = None
         self.zone_totals = None
+        self.camera_totals = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -433,6 +435,14 @@ class ModuleApp:
 
                     self.model = KvZoned(self.model, build_zone_set(cfg, dev),
                                          anchor=cfg.zone_anchor)
+        if cfg.watch:
+            from ..models.watching import KvWatched
+
+            # outermost: it looks at the frames, whatever the inner model makes of them
+            size = cfg.resolved_image_size()
+            self.model = KvWatched(self.model, cfg.batch, frame_hw=cfg.frame_hw() or (size, size),
+                                   cell=cfg.watch_cell, row_step=cfg.watch_row_step,
+                                   bg_shift=cfg.watch_bg_shift, **cfg.watch_params())
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -447,6 +457,10 @@ class ModuleApp:
             from .zones import ZoneTotals
 
             self.zone_totals = ZoneTotals(self.model, cfg.lines, cfg.zones)
+        if cfg.watch:
+            from .watch import CameraTotals
+
+            self.camera_totals = CameraTotals(self.model)
         if not self.build_phases:
             # cold-start legs (tools/module_cold_start.py): model built -> tiles tuned
             # (or read from the cache) -> warmed -> graph captured
@@ -485,7 +499,7 @@ class ModuleApp:
                 if self.world > 1 else [err])
         err = next((e for e in errs if e), None)
         if err is not None:
-            self.engine = self.model = self.zone_totals = None
+            self.engine = self.model = self.zone_totals = self.camera_totals = None
             self.sim = None
             self._stop_camera()
             if previous is None:
@@ -735,7 +749,8 @@ class ModuleApp:
             top1 = out[1].to("cpu")
             vals, counts = torch.unique(top1, return_counts=True)
             order = counts.argsort(descending=True)[:5]
-            return {"top1": {str(int(vals[i])): int(counts[i]) for i in order}}
+            return {"top1": {str(int(vals[i])): int(counts[i]) for i in order},
+                    **self._cameras_summary(out)}
         cnt = out[1].to("cpu")
         res = {"detections": {"total": int(cnt.sum()), "max_per_image": int(cnt.max())}}
         if self.cfg.model == "detect-classify":
@@ -751,7 +766,17 @@ class ModuleApp:
                              "dropped": int(st.dropped.sum())}
         if self.zone_totals is not None:  # line crossings / zone counts, over all cameras
             res.update(self.zone_totals.update().summed())
+        res.update(self._cameras_summary(out))
         return res
+
+    def _cameras_summary(self, out) -> Dict[str, Any]:
+        """Frame watch: cameras whose alarm is on now, and the alarms raised so far."""
+        if self.camera_totals is None:
+            return {}
+        from .watch import alarm_counts
+
+        return {"cameras": alarm_counts(out[-2]),
+                "camera_alarms": self.camera_totals.update().summed()}
 
     # ---------------------------------------------------------------- handlers
     # Handlers run on the module thread from transport.poll(); they only queue work
@@ -773,6 +798,10 @@ class ModuleApp:
             return 400, {"error": f"rejected patch: {e}"}
         old = self.cfg
         self.cfg = replace(new, world_size=old.world_size, sync_every=old.sync_every)
+        if (self.camera_totals is not None and not self.cfg.needs_rebuild(old)
+                and self.cfg.watch_params() != old.watch_params()):
+            # thresholds live in device memory: the captured step reads them every replay
+            self.model.watch_state.set_params(None, **self.cfg.watch_params())
         if self.cfg.needs_rebuild(old):
             self.state["rebuilds"] += 1
             log_event(self.log, "rebuild", model=self.cfg.model, batch=self.cfg.batch)
@@ -830,6 +859,12 @@ class ModuleApp:
                 if self.zone_totals is None:
                     return 400, {"error": "no lines or zones configured"}
                 return 200, {"cameras": self.zone_totals.update().per_camera(),
+                             "rank": self.rank}
+            if name == "cameras":  # the frame watch, per camera
+                if self.camera_totals is None or self.engine.outputs is None:
+                    return 400, {"error": "watch is off"}
+                self.camera_totals.update()
+                return 200, {"cameras": self.camera_totals.per_camera(self.engine.outputs[-2]),
                              "rank": self.rank}
             if name in ("reconfigure", "benchmark"):
                 if self.rank != 0:

@@ -113,6 +113,24 @@ class ModuleConfig:
     lines: Tuple[Dict[str, Any], ...] = ()
     zones: Tuple[Dict[str, Any], ...] = ()
     zone_anchor: str = "bottom"
+    # per-camera frame watch (ops.frame_watch): one more streaming pass over the incoming
+    # frames, one batch row = one camera.  A motion grid of watch_cell-pixel cells against a
+    # running background (background = mean of about 2^watch_bg_shift frames; every
+    # watch_row_step-th row is read) and five conditions -- motion / scene (watch_motion_share /
+    # watch_scene_share of the cells moved by more than watch_motion_level luma levels), dark
+    # (mean luma below watch_dark_level), flat (mean neighbour difference below
+    # watch_flat_level: covered, defocused, fogged), frozen (the frame repeats) -- each an
+    # alarm once it has held for watch_hold frames
+    watch: bool = False
+    watch_cell: int = 16
+    watch_row_step: int = 1
+    watch_bg_shift: int = 4
+    watch_motion_level: float = 10.0
+    watch_motion_share: float = 0.01
+    watch_scene_share: float = 0.5
+    watch_dark_level: float = 24.0
+    watch_flat_level: float = 1.5
+    watch_hold: int = 8
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -133,7 +151,8 @@ class ModuleConfig:
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
                "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
                "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
-               "lines", "zones", "zone_anchor")
+               "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
+               "watch_bg_shift")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
@@ -208,6 +227,23 @@ class ModuleConfig:
                                      f"{len(r['polygon'])}")
         if (self.lines or self.zones) and not self.track:
             raise ValueError("lines / zones count tracked objects: they need track true")
+        # the frame-watch launcher's ranges (csrc/kernels/frame_watch.hip)
+        if self.watch_cell not in (8, 16, 32):
+            raise ValueError("watch_cell must be 8, 16 or 32")
+        if self.watch_row_step not in (1, 2, 4):
+            raise ValueError("watch_row_step must be 1, 2 or 4")
+        if not 0 <= self.watch_bg_shift <= 8:
+            raise ValueError("watch_bg_shift must be 0..8")
+        if not 0.0 <= self.watch_motion_level <= 255.0:
+            raise ValueError("watch_motion_level must be 0..255 luma levels")
+        if not (0.0 <= self.watch_motion_share <= 1.0 and 0.0 <= self.watch_scene_share <= 1.0):
+            raise ValueError("watch_motion_share / watch_scene_share must be in [0, 1]")
+        if not (0.0 <= self.watch_dark_level <= 256.0 and 0.0 <= self.watch_flat_level <= 256.0):
+            raise ValueError("watch_dark_level / watch_flat_level must be 0..256")
+        if not 1 <= self.watch_hold <= 255:
+            raise ValueError("watch_hold must be 1..255")
+        if self.watch and self.model == "simulated-temperature":
+            raise ValueError("watch needs frames: a vision model")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -260,6 +296,23 @@ class ModuleConfig:
 
     TRACK_KEYS = ("track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
     ZONE_KEYS = ("lines", "zones", "zone_anchor")
+    WATCH_KEYS = ("watch", "watch_cell", "watch_row_step", "watch_bg_shift",
+                  "watch_motion_level", "watch_motion_share", "watch_scene_share",
+                  "watch_dark_level", "watch_flat_level", "watch_hold")
+
+    def watch_params(self) -> Dict[str, int]:
+        """The threshold words of ops.WatchState.set_params: levels in 1/16 luma
+        (floor(level * 16 + 0.5)), shares in 1/1024 of the cells."""
+        import math
+
+        def q(v, scale):
+            return int(math.floor(float(v) * scale + 0.5))
+
+        return {"motion_thr16": q(self.watch_motion_level, 16),
+                "motion_share_q": q(self.watch_motion_share, 1024),
+                "scene_share_q": q(self.watch_scene_share, 1024),
+                "dark16": q(self.watch_dark_level, 16), "flat16": q(self.watch_flat_level, 16),
+                "hold": int(self.watch_hold)}
 
     def to_dict(self) -> Dict[str, Any]:
         """The reported / saved config.  The tracking keys are listed once any of them has
@@ -276,4 +329,8 @@ class ModuleConfig:
                 d.pop(k)
         else:
             d["lines"], d["zones"] = list(d["lines"]), list(d["zones"])
+        # and the frame-watch keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.WATCH_KEYS):
+            for k in self.WATCH_KEYS:
+                d.pop(k)
         return d

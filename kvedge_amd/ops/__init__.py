@@ -1253,6 +1253,171 @@ def zone_update(det: torch.Tensor, count: torch.Tensor, track_state: TrackState,
     return out_mask, out_counts
 
 
+# ---------------------------------------------------------------------------
+# frame watch: the frames themselves -> motion grid, dark / flat / frozen / scene alarms
+# ---------------------------------------------------------------------------
+WATCH_CELLS = (8, 16, 32)
+WATCH_ROW_STEPS = (1, 2, 4)
+WATCH_MAX_BG_SHIFT = 8
+WATCH_MAX_EXTENT = 4096
+WATCH_CONDITIONS = _ref.WATCH_CONDITIONS
+WATCH_PARAMS = _ref.WATCH_PARAMS
+WATCH_PARAM_RANGES = _ref.WATCH_PARAM_RANGES
+WATCH_STATS = ("mean16", "sharp16", "moving", "cells", "conditions", "alarms")
+WATCH_HEADER = 24
+# motion 10 luma levels in 1 % of the cells, scene change at half of them, dark below level
+# 24, flat below a mean neighbour difference of 1.5 levels, alarms after 8 frames
+WATCH_DEFAULTS = {"motion_thr16": 160, "motion_share_q": 10, "scene_share_q": 512,
+                  "dark16": 384, "flat16": 24, "hold": 8}
+
+
+def watch_level16(level: float) -> int:
+    """A luma (or gradient) level in 1/16: floor(level * 16 + 0.5)."""
+    import math
+
+    return int(math.floor(float(level) * 16 + 0.5))
+
+
+def watch_share_q(share: float) -> int:
+    """A share of the cells in 1/1024: floor(share * 1024 + 0.5)."""
+    import math
+
+    return int(math.floor(float(share) * 1024 + 0.5))
+
+
+def check_watch_params(**params) -> dict:
+    """Range-check threshold words by name (``WATCH_PARAMS``) against the ranges the kernel
+    clamps them into; returns them as ints."""
+    out = {}
+    for name, v in params.items():
+        if name not in WATCH_PARAMS:
+            raise ValueError(f"unknown watch parameter {name!r}; known: {WATCH_PARAMS}")
+        lo, hi = WATCH_PARAM_RANGES[WATCH_PARAMS.index(name)]
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"watch parameter {name} = {v!r} outside {lo}..{hi}")
+        out[name] = v
+    return out
+
+
+class WatchState:
+    """Frame-watch state of ``streams`` cameras of ``frame_hw`` = (Hs, Ws) pixels: one int32
+    buffer ``buf`` [streams, 24 + 3 * GH * GW] (the layout csrc/kernels/frame_watch.hip reads),
+    GH = ceil(Hs / cell), GW = ceil(Ws / cell), and named views into it: ``primed`` [S],
+    ``run`` / ``raised`` [S, 5] (in the order of ``WATCH_CONDITIONS``; ``raised`` wraps modulo
+    2^32), ``params`` [S, 6] (``WATCH_PARAMS``: the thresholds the kernel reads every step, so
+    :meth:`set_params` takes effect from the next step without recapturing), ``acc`` / ``sum`` /
+    ``grad`` [S, GH, GW] (the background accumulator, scaled by 2^bg_shift, and the last
+    frame's per-cell sums).  ``cell`` in 8 / 16 / 32, ``row_step`` in 1 / 2 / 4 (every
+    row_step-th frame row is read), ``bg_shift`` k in 0..8 (background = acc >> k; 0 = plain
+    frame differencing)."""
+
+    def __init__(self, streams: int, frame_hw, cell: int = 16, row_step: int = 1,
+                 bg_shift: int = 4, device="cpu"):
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        hs, ws = int(frame_hw[0]), int(frame_hw[1])
+        if not (1 <= hs <= WATCH_MAX_EXTENT and 2 <= ws <= WATCH_MAX_EXTENT):
+            raise ValueError(f"frame_watch frames are 1..{WATCH_MAX_EXTENT} x "
+                             f"2..{WATCH_MAX_EXTENT}, got {hs}x{ws}")
+        if cell not in WATCH_CELLS:
+            raise ValueError(f"cell must be one of {WATCH_CELLS}, got {cell}")
+        if row_step not in WATCH_ROW_STEPS:
+            raise ValueError(f"row_step must be one of {WATCH_ROW_STEPS}, got {row_step}")
+        if isinstance(bg_shift, bool) or not 0 <= int(bg_shift) <= WATCH_MAX_BG_SHIFT:
+            raise ValueError(f"bg_shift {bg_shift} outside 0..{WATCH_MAX_BG_SHIFT}")
+        self.streams, self.frame_hw = int(streams), (hs, ws)
+        self.cell, self.row_step, self.bg_shift = int(cell), int(row_step), int(bg_shift)
+        self.grid = (-(-hs // self.cell), -(-ws // self.cell))
+        C = self.grid[0] * self.grid[1]
+        H = WATCH_HEADER
+        self.buf = torch.zeros(self.streams, H + 3 * C, dtype=torch.int32, device=device)
+        self.primed = self.buf[:, 0]
+        self.run = self.buf[:, 1:6]
+        self.raised = self.buf[:, 6:11]
+        self.params = self.buf[:, 16:22]
+        self.acc = self.buf[:, H:H + C].unflatten(1, self.grid)
+        self.sum = self.buf[:, H + C:H + 2 * C].unflatten(1, self.grid)
+        self.grad = self.buf[:, H + 2 * C:].unflatten(1, self.grid)
+        self.set_params(None, **WATCH_DEFAULTS)
+
+    @property
+    def device(self) -> torch.device:
+        return self.buf.device
+
+    def reset(self) -> "WatchState":
+        """Forget the background, the last frame and every counter; the thresholds stay
+        (device ops on the current stream)."""
+        self.buf[:, :16].zero_()
+        self.buf[:, WATCH_HEADER:].zero_()
+        return self
+
+    def set_params(self, camera=None, **params) -> "WatchState":
+        """Set thresholds of ``camera`` (None: of every camera) by name: ``motion_thr16``
+        (1/16 luma, 0..4080), ``motion_share_q`` / ``scene_share_q`` (1/1024 of the cells,
+        0..1024), ``dark16`` / ``flat16`` (1/16 luma, 0..4096), ``hold`` (frames, 1..255)."""
+        vals = check_watch_params(**params)
+        if camera is None:
+            rows = slice(None)
+        elif not 0 <= int(camera) < self.streams:
+            raise ValueError(f"camera {camera} outside 0..{self.streams - 1}")
+        else:
+            rows = slice(int(camera), int(camera) + 1)
+        for name, v in vals.items():
+            self.params[rows, WATCH_PARAMS.index(name)] = v
+        return self
+
+
+def frame_watch(src: torch.Tensor, state: WatchState, slot0: int = 0, src_format: str = "rgb",
+                out_stats: Optional[torch.Tensor] = None,
+                out_mask: Optional[torch.Tensor] = None):
+    """One frame-watch step: batch row n of ``src`` -- uint8 RGB [N, Hs, Ws, 3], or NV12
+    [N, Hs * 3 // 2, Ws] with ``src_format="nv12"`` (only the luma rows are read) -- is the next
+    frame of stream ``slot0 + n`` of ``state``.  Returns ``(stats, motion_mask)``: int32 [N, 16]
+    = mean16, sharp16, moving, cells, conditions, alarms, run[5], raised[5] (bits and counters
+    in the order of ``WATCH_CONDITIONS``) and uint8 [N, GH, GW], 1 where the cell moved against
+    the running background.  Every element of both is written; streams outside
+    [slot0, slot0 + N) are not touched.  Integer arithmetic: GPU
+    (csrc/kernels/frame_watch.hip) and CPU (ops.reference.frame_watch, where the rules are
+    written out) are bit-identical."""
+    if not isinstance(state, WatchState):
+        raise TypeError(f"state must be an ops.WatchState, got {type(state).__name__}")
+    _check_format(src_format)
+    if src.dtype != torch.uint8:
+        raise ValueError(f"frames must be uint8, got {src.dtype}")
+    if src_format == "nv12":
+        hw = _check_nv12(src)
+    else:
+        if src.dim() != 4 or src.shape[3] != 3:
+            raise ValueError(f"RGB frames are uint8 [N, Hs, Ws, 3], got {tuple(src.shape)}")
+        hw = (int(src.shape[1]), int(src.shape[2]))
+    if hw != state.frame_hw:
+        raise ValueError(f"frames of {hw[0]}x{hw[1]}, the state was made for "
+                         f"{state.frame_hw[0]}x{state.frame_hw[1]}")
+    if not src.is_contiguous():
+        raise ValueError("frames must be contiguous")
+    if src.device != state.device:
+        raise ValueError(f"frames on {src.device}, state on {state.device}")
+    n = int(src.shape[0])
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > state.streams:
+        raise ValueError(f"streams [{slot0}, {slot0 + n}) outside the state's {state.streams}")
+    if out_stats is None:
+        out_stats = empty(n, 16, dtype=torch.int32, device=src.device)
+    if out_mask is None:
+        out_mask = empty(n, *state.grid, dtype=torch.uint8, device=src.device)
+    for name, t, dt, shape in (("out_stats", out_stats, torch.int32, (n, 16)),
+                               ("out_mask", out_mask, torch.uint8, (n, *state.grid))):
+        if (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != src.device):
+            raise ValueError(f"{name} must be contiguous {dt} {list(shape)} on {src.device}")
+    if src.is_cuda:
+        _native().frame_watch(src, state.buf, out_stats, out_mask, slot0, src_format == "nv12",
+                              state.cell, state.row_step, state.bg_shift)
+    else:
+        _ref.frame_watch(src, state, slot0, src_format, out_stats, out_mask)
+    return out_stats, out_mask
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

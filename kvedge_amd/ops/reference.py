@@ -527,6 +527,109 @@ def zone_update(det, count, track_state, zone_state, zones, slot0, out_mask, out
     return out_mask, out_counts
 
 
+WATCH_CONDITIONS = ("motion", "scene", "dark", "flat", "frozen")
+WATCH_PARAMS = ("motion_thr16", "motion_share_q", "scene_share_q", "dark16", "flat16", "hold")
+WATCH_PARAM_RANGES = ((0, 4080), (0, 1024), (0, 1024), (0, 4096), (0, 4096), (1, 255))
+
+
+def watch_luma(src, src_format="rgb"):
+    """Luma int32 [N, Hs, Ws] of uint8 frames: the Y plane of NV12 [N, Hs * 3 // 2, Ws] as it
+    is (the chroma rows are never read), (77 R + 150 G + 29 B + 128) >> 8 of RGB [N, Hs, Ws, 3]."""
+    if src_format == "nv12":
+        return src[:, :src.shape[1] * 2 // 3].to(torch.int32)
+    c = src.to(torch.int32)
+    return (77 * c[..., 0] + 150 * c[..., 1] + 29 * c[..., 2] + 128) >> 8
+
+
+def watch_cells(luma, cell, row_step):
+    """Per-cell (n, sum, grad, pairs), int64 [N, GH, GW] each, of luma [N, Hs, Ws]: over the
+    sampled rows y % row_step == 0 of every cell x cell pixel cell (the last row / column of
+    cells may be partial), n the sampled pixels, sum their luma, grad the sum of
+    |Y(x+1, y) - Y(x, y)| over horizontal neighbours both in the cell, pairs their number."""
+    N, Hs, Ws = luma.shape
+    GH, GW = -(-Hs // cell), -(-Ws // cell)
+    ch = cell // row_step  # sampled rows of a whole cell (row_step divides cell)
+    y = luma[:, ::row_step].to(torch.int64)
+    one = torch.ones_like(y)
+    d = (y[:, :, 1:] - y[:, :, :-1]).abs()
+    inside = (torch.arange(Ws - 1) % cell != cell - 1).to(torch.int64)  # left pixel not last
+    d = d * inside
+    dn = one[:, :, 1:] * inside
+
+    def cells(t):
+        t = torch.nn.functional.pad(t, (0, GW * cell - t.shape[2], 0, GH * ch - t.shape[1]))
+        return t.reshape(N, GH, ch, GW, cell).sum(dim=(2, 4))
+
+    return cells(one), cells(y), cells(d), cells(dn)
+
+
+def frame_watch(src, state, slot0, src_format, out_stats, out_mask):
+    """Per-camera frame watch: THE definition the HIP kernel (csrc/kernels/frame_watch.hip)
+    equals bit for bit.  ``src`` uint8 RGB [N, Hs, Ws, 3] or NV12 [N, Hs * 3 // 2, Ws];
+    ``state`` an ops.WatchState on the CPU (cell, row_step, bg_shift k and the per-stream
+    threshold row ``params``); row n is the next frame of stream ``slot0 + n``.  All integer.
+
+    Per cell (watch_cells): v = (16 sum + n // 2) // n in 1/16 luma.  On a primed stream the
+    cell moved when |v - (acc >> k)| > motion_thr16 -- the background from before this frame --
+    and then acc += v - (acc >> k); on an unprimed stream acc = v << k and no cell moves.  The
+    stream is frozen when it is primed and every cell's (sum, grad) equals the stored pair; the
+    pairs are then stored and the stream is primed.
+
+    Per camera (Python ints, so exact): mean16 = (16 S_sum + P // 2) // P over the P sampled
+    pixels, sharp16 = (16 S_grad + Q // 2) // Q over the Q pairs, moving = moved cells, cells =
+    GH GW.  Conditions: bit 0 motion = moving > 0 and moving * 1024 >= motion_share_q * cells,
+    bit 1 scene the same with scene_share_q, bit 2 dark = mean16 < dark16, bit 3 flat =
+    sharp16 < flat16, bit 4 frozen.  run[c] = min(run[c] + 1, 65535) while the condition holds,
+    else 0; alarm bit c = run[c] >= hold; raised[c] (wrapping int32) += 1 in the frame where
+    run[c] == hold.  The thresholds are clamped into WATCH_PARAM_RANGES whatever the row holds.
+
+    out_stats [N, 16] = mean16, sharp16, moving, cells, conditions, alarms, run[5], raised[5];
+    out_mask uint8 [N, GH, GW] = 1 where the cell moved."""
+    k = state.bg_shift
+    n_px, c_sum, c_grad, c_pairs = watch_cells(watch_luma(src, src_format), state.cell,
+                                               state.row_step)
+    v = (16 * c_sum + n_px // 2) // n_px
+    for n in range(src.shape[0]):
+        s = slot0 + n
+        par = [min(max(int(p), lo), hi)
+               for p, (lo, hi) in zip(state.params[s].tolist(), WATCH_PARAM_RANGES)]
+        thr, share_m, share_s, dark16, flat16, hold = par
+        primed = int(state.primed[s]) != 0
+        acc = state.acc[s].to(torch.int64)
+        bg = acc >> k
+        if primed:
+            moved = (v[n] - bg).abs() > thr
+            acc = acc + v[n] - bg
+        else:
+            moved = torch.zeros_like(v[n], dtype=torch.bool)
+            acc = v[n] << k
+        same = bool((state.sum[s] == c_sum[n]).all() and (state.grad[s] == c_grad[n]).all())
+        state.acc[s] = acc.to(torch.int32)
+        state.sum[s] = c_sum[n].to(torch.int32)
+        state.grad[s] = c_grad[n].to(torch.int32)
+        P, Q = int(n_px[n].sum()), int(c_pairs[n].sum())
+        mean16 = (16 * int(c_sum[n].sum()) + P // 2) // P
+        sharp16 = (16 * int(c_grad[n].sum()) + Q // 2) // Q
+        moving, cells = int(moved.sum()), moved.numel()
+        cond = [moving > 0 and moving * 1024 >= share_m * cells,
+                moving > 0 and moving * 1024 >= share_s * cells,
+                mean16 < dark16, sharp16 < flat16, primed and same]
+        bits = alarms = 0
+        for c, on in enumerate(cond):
+            run = min(int(state.run[s, c]) + 1, 65535) if on else 0
+            bits |= int(on) << c
+            alarms |= int(run >= hold) << c
+            if run == hold:
+                state.raised[s, c] = _wrap32(int(state.raised[s, c]) + 1)
+            state.run[s, c] = run
+        state.primed[s] = 1
+        out_stats[n] = torch.tensor([mean16, sharp16, moving, cells, bits, alarms]
+                                    + state.run[s].tolist() + state.raised[s].tolist(),
+                                    dtype=torch.int32)
+        out_mask[n] = moved.to(torch.uint8)
+    return out_stats, out_mask
+
+
 def conv_dual2(x, x_coff, K1, x2, x2_coff, w, bias, act, stride2, up2, out, y_coff):
     K2 = w.shape[1] - K1
     a = x[..., x_coff:x_coff + K1].float()
