@@ -6,7 +6,8 @@ timed with every tile of the kernel tile table -- v1 register-staged and v2 LDS-
 families -- (HIP events, median of a few launches) and the fastest valid tile is pinned
 on the layer before hipGraph capture.  Tiles a layer cannot use (e.g. the fused
 downsample GEMM on a v1 tile) are skipped.  Correctness never depends on the tile
-(tests/test_kernels_gpu.py::test_conv_every_tile).
+(tests/test_kernels_gpu.py::test_conv_every_tile on synthetic shapes;
+tests/test_model_walk_gpu.py::test_tile_sweep at the two models' own layer keys and operands).
 """
 from __future__ import annotations
 
