@@ -958,6 +958,64 @@ void frame_watch(const at::Tensor& src, at::Tensor& state, at::Tensor& stats, at
   TORCH_CHECK(rc == 0, "kvedge: frame_watch failed rc=", rc);
 }
 
+// K21: baseline JPEG encoder (csrc/kernels/jpeg_encode.hip).  images uint8 [M,H,W,3]; the
+// tables, the header and the workspaces belong to an ops.JpegEncoder made for (H, W) and the
+// subsampling; out uint8 [rows >= M, cap], length int32 [rows].  Everything is validated before
+// the first launch.
+void jpeg_encode(const at::Tensor& images, const at::Tensor& qtab, const at::Tensor& huff,
+                 const at::Tensor& header, at::Tensor& coef, at::Tensor& scratch,
+                 at::Tensor& seglen, at::Tensor& out, at::Tensor& length, bool sub420) {
+  check_dev(images, "images");
+  check_dev(qtab, "qtab");
+  check_dev(huff, "huff");
+  check_dev(header, "header");
+  check_dev(coef, "coef");
+  check_dev(scratch, "scratch");
+  check_dev(seglen, "seglen");
+  check_dev(out, "out");
+  check_dev(length, "length");
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 &&
+                  images.is_contiguous(), "kvedge: jpeg_encode images uint8 [M,H,W,3] contiguous");
+  const int64_t M = images.size(0), H = images.size(1), W = images.size(2);
+  TORCH_CHECK(H >= 1 && H <= 8192 && W >= 1 && W <= 8192,
+              "kvedge: jpeg_encode image size 1..8192, got ", H, "x", W);
+  const int64_t mcu = sub420 ? 16 : 8;
+  const int64_t mh = (H + mcu - 1) / mcu, nb = (W + mcu - 1) / mcu * (sub420 ? 6 : 3);
+  const int64_t seg_cap = nb * kv_jpeg_block_bytes() + 16;
+  TORCH_CHECK(qtab.scalar_type() == at::kInt && qtab.numel() == 128 && qtab.is_contiguous(),
+              "kvedge: jpeg_encode qtab int32 [2,64]");
+  TORCH_CHECK(huff.scalar_type() == at::kInt && huff.numel() == 1024 && huff.is_contiguous(),
+              "kvedge: jpeg_encode huff int32 [4,256]");
+  TORCH_CHECK(header.scalar_type() == at::kByte && header.numel() == kv_jpeg_header_bytes() &&
+                  header.is_contiguous(), "kvedge: jpeg_encode header uint8 [",
+              kv_jpeg_header_bytes(), "]");
+  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.is_contiguous() &&
+                  coef.numel() >= M * mh * nb * 64, "kvedge: jpeg_encode coef int16 [M,", mh, ",",
+              nb, ",64]");
+  TORCH_CHECK(scratch.scalar_type() == at::kByte && scratch.is_contiguous() &&
+                  scratch.numel() >= M * mh * seg_cap, "kvedge: jpeg_encode scratch uint8 [M,",
+              mh, ",", seg_cap, "]");
+  TORCH_CHECK(seglen.scalar_type() == at::kInt && seglen.is_contiguous() &&
+                  seglen.numel() >= M * mh, "kvedge: jpeg_encode seglen int32 [M,", mh, "]");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 2 && out.is_contiguous() &&
+                  out.size(0) >= M && out.size(1) >= 1 && out.size(1) <= 0x7fffffffll,
+              "kvedge: jpeg_encode out uint8 [>= M, cap] contiguous");
+  TORCH_CHECK(length.scalar_type() == at::kInt && length.dim() == 1 && length.is_contiguous() &&
+                  length.size(0) >= M, "kvedge: jpeg_encode length int32 [>= M]");
+  TORCH_CHECK(M <= 65535, "kvedge: jpeg_encode too many images");
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{
+           &qtab, &huff, &header, &coef, &scratch, &seglen, &out, &length})
+    TORCH_CHECK(t->device() == images.device(), "kvedge: jpeg_encode operands on different devices");
+  const c10::DeviceGuard g(images.device());
+  const int rc = kv_jpeg_encode(images.data_ptr<uint8_t>(), qtab.data_ptr<int>(),
+                                huff.data_ptr<int>(), header.data_ptr<uint8_t>(),
+                                coef.data_ptr<int16_t>(), scratch.data_ptr<uint8_t>(),
+                                seglen.data_ptr<int>(), out.data_ptr<uint8_t>(),
+                                length.data_ptr<int>(), (int)M, (int)H, (int)W, sub420 ? 1 : 0,
+                                (long long)out.size(1), cur_stream(images));
+  TORCH_CHECK(rc == 0, "kvedge: jpeg_encode failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -1084,6 +1142,9 @@ TORCH_LIBRARY(kvedge, m) {
         "Tensor table, Tensor(b!) zone_mask, Tensor(c!) zone_counts, int slot0) -> ()");
   m.def("frame_watch(Tensor src, Tensor(a!) state, Tensor(b!) stats, Tensor(c!) mask, int slot0, "
         "bool nv12, int cell, int row_step, int bg_shift) -> ()");
+  m.def("jpeg_encode(Tensor images, Tensor qtab, Tensor huff, Tensor header, Tensor(a!) coef, "
+        "Tensor(b!) scratch, Tensor(c!) seglen, Tensor(d!) out, Tensor(e!) length, bool sub420) "
+        "-> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1131,6 +1192,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("track_update", track_update);
   m.impl("zone_update", zone_update);
   m.impl("frame_watch", frame_watch);
+  m.impl("jpeg_encode", jpeg_encode);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

@@ -234,6 +234,23 @@ int kv_watch_state_stride(int cells);
 int kv_frame_watch(const unsigned char* src, int* state, int* stats, unsigned char* mask, int N,
                    int S, int slot0, int Hs, int Ws, int nv12, int cell, int row_step,
                    int bg_shift, hipStream_t s);
+// K21 (jpeg_encode.hip): baseline JPEG files of images uint8 RGB [M,H,W,3], three launches.
+// qtab int32 [2,64] (luminance, chrominance quantisers in natural order, clamped to 1..255),
+// huff int32 [4,256] (code | length << 16 by symbol: DC lum, DC chroma, AC lum, AC chroma) and
+// header uint8 [kv_jpeg_header_bytes()] are read from device memory at run time.  Workspaces,
+// with mcu = 16 (sub420) or 8, mh = ceil(H / mcu), nb = ceil(W / mcu) * (6 | 3): coef int16
+// [M,mh,nb,64] (16-byte aligned), scratch uint8 [M,mh,nb * kv_jpeg_block_bytes() + 16], seglen
+// int32 [M,mh].  out uint8 rows of cap bytes: row m gets file m and length[m] its size, or
+// length[m] = -size and no byte of the row when size > cap; bytes past the file are left alone.
+// Byte-identical to ops.reference.jpeg_encode; the format is at the top of jpeg_encode.hip.
+// Returns -1 H or W outside 1..8192, -2 M outside 0..65535, -3 cap outside 1..2^31-1, -4 the
+// worst-case file exceeds 2^31-1 bytes, -7 misaligned operand.  M == 0 launches nothing.
+int kv_jpeg_header_bytes(void);
+int kv_jpeg_block_bytes(void);
+int kv_jpeg_encode(const unsigned char* images, const int* qtab, const int* huff,
+                   const unsigned char* header, short* coef, unsigned char* scratch, int* seglen,
+                   unsigned char* out, int* length, int M, int H, int W, int sub420,
+                   long long cap, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

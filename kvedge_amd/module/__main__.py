@@ -125,6 +125,20 @@ def main(argv=None):
                     help="mean neighbour difference below which the picture is `flat`")
     ap.add_argument("--watch-hold", type=int, default=d.watch_hold,
                     help="frames a condition must hold before its alarm (1..255)")
+    ap.add_argument("--snapshots", action="store_true",
+                    help="encode every camera's frame as a JPEG thumbnail on the device; "
+                         "pictures leave on output `snapshots` with watch alarms and "
+                         "periodically, and through direct method `snapshot`")
+    ap.add_argument("--snapshot-width", type=int, default=d.snapshot_width,
+                    help="thumbnail width, pixels (16..1920; the height follows the frame)")
+    ap.add_argument("--snapshot-subsampling", default=d.snapshot_subsampling,
+                    choices=["420", "444"], help="chroma subsampling of the JPEG")
+    ap.add_argument("--snapshot-quality", type=int, default=d.snapshot_quality,
+                    help="JPEG quality 1..100 (changes without a rebuild)")
+    ap.add_argument("--snapshot-every-s", type=float, default=d.snapshot_every_s,
+                    help="seconds between periodic pictures per camera (0 = never)")
+    ap.add_argument("--snapshot-max-bytes", type=int, default=d.snapshot_max_bytes,
+                    help="a larger picture is counted as oversize, not sent")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -170,7 +184,12 @@ def main(argv=None):
                        watch_motion_share=a.watch_motion_share,
                        watch_scene_share=a.watch_scene_share,
                        watch_dark_level=a.watch_dark_level,
-                       watch_flat_level=a.watch_flat_level, watch_hold=a.watch_hold).validate()
+                       watch_flat_level=a.watch_flat_level, watch_hold=a.watch_hold,
+                       snapshots=a.snapshots, snapshot_width=a.snapshot_width,
+                       snapshot_subsampling=a.snapshot_subsampling,
+                       snapshot_quality=a.snapshot_quality,
+                       snapshot_every_s=a.snapshot_every_s,
+                       snapshot_max_bytes=a.snapshot_max_bytes).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -16,7 +16,11 @@ but the workload is ResNet-50 / YOLOv8n on the passed-through MI355X:
              updated; invalid patches are rejected and reported, never crash the loop;
              a rebuild that fails (e.g. out of HBM) rolls back to the previous config
              and reports ``lastError``.
-  direct methods: benchmark {steps, warmup}, getStatus, reconfigure {...}, ping.
+  direct methods: benchmark {steps, warmup}, getStatus, reconfigure {...}, ping,
+             zones, cameras, snapshot {camera}.
+  snapshots: with `snapshots` on, every camera's frame is a JPEG thumbnail on the device after
+             each step; a picture leaves on output "snapshots" when a watch alarm is raised
+             for its camera, and periodically (module/snapshots.py).
 
 Multi-replica lockstep (world_size > 1, one rank per GPU/VM).  Every collective a rank
 issues must be issued by every other rank in the same order, but twin patches, method
@@ -196,6 +200,7 @@ class ModuleApp:
         self.model = None
         self.zone_totals = None  # module.zones.ZoneTotals once lines / zones are configured
         self.camera_totals = None  # module.watch.CameraTotals with `watch` on
+        self.snapshots = None  # module.snapshots.SnapshotSender with `snapshots` on
         self.ring = None
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
@@ -398,6 +403,7 @@ class ModuleApp:
         self.sim = None
         self.zone_totals = None
         self.camera_totals = None
+        self.snapshots = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -435,6 +441,16 @@ class ModuleApp:
 
                     self.model = KvZoned(self.model, build_zone_set(cfg, dev),
                                          anchor=cfg.zone_anchor)
+        if cfg.snapshots:
+            from ..models.snapshots import KvSnapshots
+
+            # inside the watch, so that the watch's two outputs stay the last two; a device
+            # row holds the derived worst case up to 1 MiB (a larger file is reported by size)
+            size = cfg.resolved_image_size()
+            self.model = KvSnapshots(self.model, cfg.batch, frame_hw=cfg.frame_hw() or (size, size),
+                                     width=cfg.snapshot_width,
+                                     subsampling=cfg.snapshot_subsampling,
+                                     quality=cfg.snapshot_quality, cap=1 << 20)
         if cfg.watch:
             from ..models.watching import KvWatched
 
@@ -461,6 +477,10 @@ class ModuleApp:
             from .watch import CameraTotals
 
             self.camera_totals = CameraTotals(self.model)
+        if cfg.snapshots:
+            from .snapshots import SnapshotSender
+
+            self.snapshots = SnapshotSender(self.model, cfg.batch, self.clock())
         if not self.build_phases:
             # cold-start legs (tools/module_cold_start.py): model built -> tiles tuned
             # (or read from the cache) -> warmed -> graph captured
@@ -500,7 +520,7 @@ class ModuleApp:
         err = next((e for e in errs if e), None)
         if err is not None:
             self.engine = self.model = self.zone_totals = self.camera_totals = None
-            self.sim = None
+            self.sim = self.snapshots = None
             self._stop_camera()
             if previous is None:
                 return err
@@ -571,6 +591,13 @@ class ModuleApp:
         self._win_imgs += self.cfg.batch * nsteps
         self.state["total_images"] += self.cfg.batch * nsteps
         self.state["total_steps"] += nsteps
+        if self.snapshots is not None and nsteps > 0 and self.engine.outputs is not None:
+            # the pictures of the last step: lengths to the host, bytes only for what is sent
+            totals = self.camera_totals.update() if self.camera_totals is not None else None
+            self.snapshots.step(self.engine.outputs, totals, self.clock(),
+                                self.state["total_steps"], self.cfg.snapshot_every_s,
+                                self.cfg.snapshot_max_bytes,
+                                lambda m: self.tr.send_message("snapshots", m))
         if not self._first_inference_stamped and nsteps > 0:
             self._first_inference_stamped = True
             self._stamp("module_first_inference")
@@ -729,6 +756,8 @@ class ModuleApp:
             if g:
                 msg["gpu"] = g
         msg.update(self._outputs_summary())
+        if self.snapshots is not None:
+            msg["snapshots"] = self.snapshots.summary()
         if self.rank == 0:
             self.tr.send_message("telemetry", msg)
             self.state["messages"] += 1
@@ -802,6 +831,10 @@ class ModuleApp:
                 and self.cfg.watch_params() != old.watch_params()):
             # thresholds live in device memory: the captured step reads them every replay
             self.model.watch_state.set_params(None, **self.cfg.watch_params())
+        if (self.snapshots is not None and not self.cfg.needs_rebuild(old)
+                and self.cfg.snapshot_quality != old.snapshot_quality):
+            # the quantisation tables live in device memory, like the watch thresholds
+            self.snapshots.stage.set_quality(self.cfg.snapshot_quality)
         if self.cfg.needs_rebuild(old):
             self.state["rebuilds"] += 1
             log_event(self.log, "rebuild", model=self.cfg.model, batch=self.cfg.batch)
@@ -866,6 +899,11 @@ class ModuleApp:
                 self.camera_totals.update()
                 return 200, {"cameras": self.camera_totals.per_camera(self.engine.outputs[-2]),
                              "rank": self.rank}
+            if name == "snapshot":  # {camera: n}: that camera's picture of the last step
+                if self.snapshots is None or self.engine is None:
+                    return 400, {"error": "snapshots are off"}
+                return self.snapshots.method(self.engine.outputs, payload,
+                                             self.cfg.snapshot_max_bytes)
             if name in ("reconfigure", "benchmark"):
                 if self.rank != 0:
                     return 409, {"error": NOT_CONTROL_POINT.format(rank=self.rank)}

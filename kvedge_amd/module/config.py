@@ -17,6 +17,7 @@ SOURCES = ("synthetic", "camera", "camera-nv12")
 DTYPES = ("bf16",)
 ZONE_ANCHORS = ("bottom", "centre")
 MAX_REGIONS = 8  # lines, and zones, per camera (csrc/kernels/zones.hip)
+SNAPSHOT_SUBSAMPLINGS = ("420", "444")
 
 
 def _point(p, what: str):
@@ -131,6 +132,19 @@ class ModuleConfig:
     watch_dark_level: float = 24.0
     watch_flat_level: float = 1.5
     watch_hold: int = 8
+    # camera snapshots (ops.jpeg_encode): every step each camera's current frame is resized on
+    # the device to snapshot_width pixels wide (the height follows the frame's shape) and
+    # encoded as a baseline JPEG of snapshot_subsampling ("420" / "444") at snapshot_quality.
+    # A picture leaves on output `snapshots` when one of the camera's watch alarms is raised
+    # and, with snapshot_every_s > 0, every snapshot_every_s seconds; one above
+    # snapshot_max_bytes is counted as oversize and not sent.  Direct method `snapshot`
+    # returns a camera's last picture
+    snapshots: bool = False
+    snapshot_width: int = 320
+    snapshot_subsampling: str = "420"
+    snapshot_quality: int = 75
+    snapshot_every_s: float = 0.0
+    snapshot_max_bytes: int = 131072
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -152,7 +166,7 @@ class ModuleConfig:
                "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
                "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
-               "watch_bg_shift")
+               "watch_bg_shift", "snapshots", "snapshot_width", "snapshot_subsampling")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
@@ -244,6 +258,19 @@ class ModuleConfig:
             raise ValueError("watch_hold must be 1..255")
         if self.watch and self.model == "simulated-temperature":
             raise ValueError("watch needs frames: a vision model")
+        if not 16 <= self.snapshot_width <= 1920:
+            raise ValueError("snapshot_width must be 16..1920")
+        if self.snapshot_subsampling not in SNAPSHOT_SUBSAMPLINGS:
+            raise ValueError(f"snapshot_subsampling must be one of {SNAPSHOT_SUBSAMPLINGS}, got "
+                             f"{self.snapshot_subsampling!r}")
+        if not 1 <= self.snapshot_quality <= 100:
+            raise ValueError("snapshot_quality must be 1..100")
+        if self.snapshot_every_s < 0:
+            raise ValueError("snapshot_every_s must be >= 0 (0 = never periodic)")
+        if self.snapshot_max_bytes < 1:
+            raise ValueError("snapshot_max_bytes must be >= 1")
+        if self.snapshots and self.model == "simulated-temperature":
+            raise ValueError("snapshots need frames: a vision model")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -300,6 +327,9 @@ class ModuleConfig:
                   "watch_motion_level", "watch_motion_share", "watch_scene_share",
                   "watch_dark_level", "watch_flat_level", "watch_hold")
 
+    SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
+                     "snapshot_every_s", "snapshot_max_bytes")
+
     def watch_params(self) -> Dict[str, int]:
         """The threshold words of ops.WatchState.set_params: levels in 1/16 luma
         (floor(level * 16 + 0.5)), shares in 1/1024 of the cells."""
@@ -332,5 +362,9 @@ class ModuleConfig:
         # and the frame-watch keys
         if all(getattr(self, k) == getattr(base, k) for k in self.WATCH_KEYS):
             for k in self.WATCH_KEYS:
+                d.pop(k)
+        # and the snapshot keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.SNAPSHOT_KEYS):
+            for k in self.SNAPSHOT_KEYS:
                 d.pop(k)
         return d

@@ -1418,6 +1418,161 @@ def frame_watch(src: torch.Tensor, state: WatchState, slot0: int = 0, src_format
     return out_stats, out_mask
 
 
+# ---------------------------------------------------------------------------
+# camera snapshots: baseline JPEG files of frames that are already on the device
+# ---------------------------------------------------------------------------
+JPEG_SUBSAMPLINGS = _ref.JPEG_SUBSAMPLINGS
+JPEG_MAX_EXTENT = 8192
+JPEG_HEADER_BYTES = _ref.JPEG_HEADER_BYTES
+JPEG_BLOCK_BYTES = 416
+
+
+def jpeg_max_bytes(hw, subsampling: str = "420") -> int:
+    """Worst-case size of a file of :func:`jpeg_encode`, derived and not measured.
+
+    One 8 x 8 block: the DC difference is a Huffman code of at most 11 bits (the longest DC code
+    of the Annex K tables, chrominance category 11) and at most 11 magnitude bits; each of the
+    63 AC coefficients costs at most a 16-bit code and 10 magnitude bits.  A ZRL (at most 16
+    bits) stands for 16 zero coefficients and an EOB for at least one, so neither can exceed the
+    26 bits per coefficient already counted: 22 + 63 * 26 = 1660 bits, 207.5 bytes.  An
+    interval of nb blocks is therefore at most nb * 208 bytes after its last byte is padded with
+    1-bits, and every one of them may be an FF that is stuffed: nb * 416.  Per interval one
+    more byte is allowed for the padding (it is already inside the bound above whenever
+    nb * 1660 is no multiple of 8; kept so that the bound does not rest on that) and 2 bytes for
+    the RSTn marker (the last interval has none); the header and the 2-byte EOI are added once."""
+    _, mh, mw, bpm = _ref.jpeg_geometry(hw, subsampling)
+    return JPEG_HEADER_BYTES + mh * (mw * bpm * JPEG_BLOCK_BYTES + 1 + 2) + 2
+
+
+def thumbnail_plan(src_hw, width: int) -> ResizePlan:
+    """Full-frame stretch of ``src_hw`` = (Hs, Ws) frames to ``width`` x round(width * Hs / Ws),
+    both rounded up to a multiple of 4 (:func:`frame_resize` needs Wd % 4 == 0); no padding."""
+    width = int(width)
+    hs, ws = _check_src_hw(src_hw, max(width, 1))
+    if width < 1:
+        raise ValueError(f"thumbnail width {width} must be >= 1")
+    wd = -(-width // 4) * 4
+    hd = -(-max(1, int(round(width * hs / ws))) // 4) * 4
+    if max(wd, hd) > RESIZE_MAX_EXTENT:
+        raise ValueError(f"thumbnail {hd}x{wd} exceeds {RESIZE_MAX_EXTENT}")
+    return ResizePlan((hs, hd, 0, 0, hd), (ws, wd, 0, 0, wd), 0, (hs, ws), (hd, wd))
+
+
+class JpegEncoder:
+    """Everything :func:`jpeg_encode` needs outside the caller's tensors, for up to
+    ``max_images`` images of ``hw`` = (H, W) pixels per call, all in device memory:
+    ``qtab`` int32 [2, 64] (luminance / chrominance quantisers, natural order), ``huff`` int32
+    [4, 256] (code | length << 16 of the four Annex K tables), ``header`` uint8 [611] (SOI, DQT
+    x2, SOF0, DHT x4, DRI, SOS) and the workspaces ``coef`` int16 [max_images, intervals,
+    blocks, 64], ``scratch`` uint8 [max_images, intervals, blocks * 416 + 16] and ``seglen``
+    int32 [max_images, intervals] (one restart interval per MCU row).  The kernels read the
+    tables and the header at run time, so :meth:`set_quality` takes effect from the next call
+    -- or the next replay of a captured step -- without recapturing."""
+
+    def __init__(self, hw, max_images: int, subsampling: str = "420", quality: int = 75,
+                 device="cpu"):
+        self.mcu, self.intervals, mw, bpm = _ref.jpeg_geometry(hw, subsampling)
+        if isinstance(max_images, bool) or int(max_images) < 1:
+            raise ValueError(f"max_images must be >= 1, got {max_images!r}")
+        self.hw = (int(hw[0]), int(hw[1]))
+        self.max_images, self.subsampling = int(max_images), subsampling
+        self.blocks = mw * bpm
+        self.max_bytes = jpeg_max_bytes(self.hw, subsampling)
+        if self.max_bytes > 2 ** 31 - 1:
+            raise ValueError(f"a {self.hw[0]}x{self.hw[1]} image can exceed 2 GiB as a file")
+        dev = torch.device(device)
+        self.qtab = torch.zeros(2, 64, dtype=torch.int32, device=dev)
+        self.huff = torch.from_numpy(_ref.jpeg_huff_codes()).to(dev)
+        self.header = torch.zeros(JPEG_HEADER_BYTES, dtype=torch.uint8, device=dev)
+        self.quality = None
+        self.set_quality(quality)
+        M, I, B = self.max_images, self.intervals, self.blocks
+        if dev.type == "cuda":
+            self.coef = torch.empty(M, I, B, 64, dtype=torch.int16, device=dev)
+            self.scratch = torch.empty(M, I, B * JPEG_BLOCK_BYTES + 16, dtype=torch.uint8,
+                                       device=dev)
+            self.seglen = torch.empty(M, I, dtype=torch.int32, device=dev)
+        else:
+            self.coef = self.scratch = self.seglen = None  # the reference needs none
+
+    @property
+    def device(self) -> torch.device:
+        return self.qtab.device
+
+    def set_quality(self, quality: int) -> "JpegEncoder":
+        """Rewrite the two quantisation tables and the header's DQT bytes for ``quality`` in
+        1..100 (copies into the existing device tensors on the current stream)."""
+        q = _ref.jpeg_quant_tables(quality)
+        head = torch.frombuffer(bytearray(_ref.jpeg_header(self.hw, self.subsampling, q)),
+                                dtype=torch.uint8)
+        if self.quality is None:
+            self.header.copy_(head)
+        else:
+            for o in _ref.JPEG_DQT_OFFSETS:
+                self.header[o:o + 64].copy_(head[o:o + 64])
+        self.qtab.copy_(torch.from_numpy(q))
+        self.quality = int(quality)
+        return self
+
+
+def jpeg_encode(images: torch.Tensor, enc: JpegEncoder, out: Optional[torch.Tensor] = None,
+                lengths: Optional[torch.Tensor] = None, slot0: int = 0):
+    """Baseline JPEG files of ``images`` uint8 [M, H, W, 3] RGB (contiguous, (H, W) == enc.hw,
+    M <= enc.max_images).  Returns ``(buf, length)``: ``buf`` uint8 [rows >= M, cap] is ``out``
+    or a new [M, jpeg_max_bytes] tensor, ``length`` int32 [rows] is ``lengths`` or new;
+    ``buf[m, :length[m]]`` is file m, complete and openable by any decoder (no JFIF segment).
+    A file that does not fit ``cap`` gives ``length[m] = -needed`` and leaves row m alone.
+    Bytes past a file and the rows past M are left as they were.  Three launches on the
+    current stream, no host synchronisation, capturable (csrc/kernels/jpeg_encode.hip); GPU
+    and CPU (ops.reference.jpeg_encode, where the format is written out) agree byte for
+    byte.  ``slot0``: image m works in rows ``slot0 + m`` of the encoder's workspaces
+    (slot0 + M <= enc.max_images), so calls on different streams may overlap when their rows
+    are disjoint -- the engine's batch slices."""
+    if not isinstance(enc, JpegEncoder):
+        raise TypeError(f"enc must be an ops.JpegEncoder, got {type(enc).__name__}")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"images are uint8 [M, H, W, 3], got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    if tuple(images.shape[1:3]) != enc.hw:
+        raise ValueError(f"images of {images.shape[1]}x{images.shape[2]}, the encoder was made "
+                         f"for {enc.hw[0]}x{enc.hw[1]}")
+    m, slot0 = int(images.shape[0]), int(slot0)
+    if slot0 < 0 or slot0 + m > enc.max_images:
+        raise ValueError(f"images [{slot0}, {slot0 + m}) outside the {enc.max_images} the "
+                         f"encoder was made for")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    if images.device != enc.device:
+        raise ValueError(f"images on {images.device}, encoder on {enc.device}")
+    if out is None:
+        out = empty(m, enc.max_bytes, dtype=torch.uint8, device=images.device)
+    if lengths is None:
+        lengths = empty(int(out.shape[0]) if out.dim() == 2 else m, dtype=torch.int32,
+                        device=images.device)
+    if (out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] < m or out.shape[1] < 1
+            or not out.is_contiguous() or out.device != images.device):
+        raise ValueError(f"out must be contiguous uint8 [>= {m}, cap] on {images.device}")
+    if (lengths.dtype != torch.int32 or lengths.dim() != 1 or lengths.shape[0] < m
+            or not lengths.is_contiguous() or lengths.device != images.device):
+        raise ValueError(f"lengths must be contiguous int32 [>= {m}] on {images.device}")
+    if images.is_cuda:
+        rows = slice(slot0, slot0 + m)
+        _native().jpeg_encode(images, enc.qtab, enc.huff, enc.header, enc.coef[rows],
+                              enc.scratch[rows], enc.seglen[rows], out, lengths,
+                              enc.subsampling == "420")
+    else:
+        files = _ref.jpeg_encode(images, enc.subsampling, qtabs=enc.qtab.numpy(),
+                                 header=bytes(enc.header.tolist()))
+        cap = int(out.shape[1])
+        for i, f in enumerate(files):
+            if len(f) > cap:
+                lengths[i] = -len(f)
+            else:
+                out[i, :len(f)] = torch.frombuffer(bytearray(f), dtype=torch.uint8)
+                lengths[i] = len(f)
+    return out, lengths
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

@@ -651,3 +651,277 @@ def conv_dual(x1, x2, w, bias, act, stride2, out):
         y = y + bias.float()
     out.copy_(_act(y, act & 3).to(out.dtype))
     return out
+
+
+# ---------------------------------------------------------------------------
+# baseline JPEG encoder (csrc/kernels/jpeg_encode.hip): the format and its tables
+# ---------------------------------------------------------------------------
+JPEG_SUBSAMPLINGS = ("420", "444")
+# zigzag position -> natural (row * 8 + column) index
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
+               41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15,
+               23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# JPEG spec Annex K.1: luminance and chrominance quantisation tables, natural order
+JPEG_QBASE = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55,
+     14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+     24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99))
+# JPEG spec Annex K.3: the four typical Huffman tables as (codes per length 1..16, symbols);
+# order: DC luminance, DC chrominance, AC luminance, AC chrominance
+JPEG_HUFF = (
+    ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61,
+      0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52,
+      0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25,
+      0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45,
+      0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64,
+      0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+      0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6,
+      0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3,
+      0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8,
+      0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61,
+      0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33,
+      0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18,
+      0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44,
+      0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63,
+      0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+      0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4,
+      0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca,
+      0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7,
+      0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)))
+JPEG_DQT_OFFSETS = (7, 76)  # of the 64 table bytes of each DQT segment in the header
+JPEG_HEADER_BYTES = 611
+
+
+def jpeg_quant_tables(quality: int) -> np.ndarray:
+    """int32 [2, 64] (luminance, chrominance; natural order): the Annex K tables scaled the
+    libjpeg way, s = 5000 // q below 50 else 200 - 2 q, entry = (base * s + 50) // 100
+    clamped to 1..255."""
+    q = int(quality)
+    if isinstance(quality, bool) or not 1 <= q <= 100:
+        raise ValueError(f"JPEG quality {quality!r} outside 1..100")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((np.asarray(JPEG_QBASE, np.int64) * s + 50) // 100, 1, 255).astype(np.int32)
+
+
+def jpeg_huff_codes() -> np.ndarray:
+    """int32 [4, 256]: code | length << 16 of every symbol of the four tables (0 where the
+    table has no such symbol), codes assigned as the spec's Annex C does."""
+    out = np.zeros((4, 256), np.int32)
+    for t, (bits, vals) in enumerate(JPEG_HUFF):
+        code, k = 0, 0
+        for ln in range(1, 17):
+            for _ in range(bits[ln - 1]):
+                out[t, vals[k]] = code | (ln << 16)
+                code += 1
+                k += 1
+            code <<= 1
+        assert k == len(vals)
+    return out
+
+
+def jpeg_geometry(hw, subsampling: str):
+    """(mcu, MCU rows = restart intervals, MCUs per row, blocks per MCU)."""
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be one of {JPEG_SUBSAMPLINGS}, got {subsampling!r}")
+    h, w = int(hw[0]), int(hw[1])
+    if not (1 <= h <= 8192 and 1 <= w <= 8192):
+        raise ValueError(f"JPEG image size {h}x{w} outside 1..8192")
+    mcu = 16 if subsampling == "420" else 8
+    return mcu, -(-h // mcu), -(-w // mcu), 6 if subsampling == "420" else 3
+
+
+def jpeg_header(hw, subsampling: str, qtabs) -> bytes:
+    """SOI, DQT x2, SOF0 (true size), DHT x4, DRI (one MCU row), SOS: JPEG_HEADER_BYTES."""
+    _, _, mw, _ = jpeg_geometry(hw, subsampling)
+    h, w = int(hw[0]), int(hw[1])
+    zz = list(JPEG_ZIGZAG)
+    out = bytearray(b"\xff\xd8")
+    for t in range(2):
+        out += b"\xff\xdb\x00\x43" + bytes([t]) + bytes(int(qtabs[t][i]) for i in zz)
+    samp = 0x22 if subsampling == "420" else 0x11
+    out += (b"\xff\xc0\x00\x11\x08" + h.to_bytes(2, "big") + w.to_bytes(2, "big") + b"\x03"
+            + bytes([1, samp, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for (bits, vals), tc_th in zip(JPEG_HUFF, (0x00, 0x01, 0x10, 0x11)):
+        out += (b"\xff\xc4" + (19 + len(vals)).to_bytes(2, "big") + bytes([tc_th]) + bytes(bits)
+                + bytes(vals))
+    out += b"\xff\xdd\x00\x04" + mw.to_bytes(2, "big")
+    out += b"\xff\xda\x00\x0c\x03" + bytes([1, 0x00, 2, 0x11, 3, 0x11]) + b"\x00\x3f\x00"
+    assert len(out) == JPEG_HEADER_BYTES
+    return bytes(out)
+
+
+def _jpeg_dct_pass(d, first: bool):
+    """One 8-point pass of the Loeffler-Ligtenberg-Moschytz forward DCT in 13-bit fixed point
+    along the last axis (int64 in, int64 out).  The first (row) pass leaves 2 extra bits, the
+    second (column) pass removes them again and leaves the factor 8 of the 2-D transform."""
+    CB, P1 = 13, 2
+    sh = CB - P1 if first else CB + P1
+
+    def descale(x, n):
+        return (x + (1 << (n - 1))) >> n
+
+    d0, d1, d2, d3, d4, d5, d6, d7 = (d[..., i] for i in range(8))
+    t0, t7, t1, t6 = d0 + d7, d0 - d7, d1 + d6, d1 - d6
+    t2, t5, t3, t4 = d2 + d5, d2 - d5, d3 + d4, d3 - d4
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    o = [None] * 8
+    if first:
+        o[0], o[4] = (t10 + t11) << P1, (t10 - t11) << P1
+    else:
+        o[0], o[4] = descale(t10 + t11, P1), descale(t10 - t11, P1)
+    z1 = (t12 + t13) * 4433
+    o[2] = descale(z1 + t13 * 6270, sh)
+    o[6] = descale(z1 - t12 * 15137, sh)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2 = z1 * -7373, z2 * -20995
+    z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
+    o[7] = descale(t4 + z1 + z3, sh)
+    o[5] = descale(t5 + z2 + z4, sh)
+    o[3] = descale(t6 + z2 + z3, sh)
+    o[1] = descale(t7 + z1 + z4, sh)
+    return np.stack(o, axis=-1)
+
+
+def jpeg_coefficients(image: np.ndarray, subsampling: str, qtabs) -> np.ndarray:
+    """Quantised zigzag coefficients int16 [intervals, blocks per interval, 64] of one uint8
+    [H, W, 3] RGB image in scan order (MCU by MCU: Y00 Y01 Y10 Y11 Cb Cr for 4:2:0, Y Cb Cr for
+    4:4:4).  JFIF full-range BT.601 in 16-bit fixed point, edge replication to whole MCUs,
+    4:2:0 chroma (a + b + c + d + 2) >> 2, level shift by 128, the integer DCT above,
+    q = sign(c) * ((|c| + 4 Q) // (8 Q)), DC clamped to +-1024 and AC to +-1023."""
+    mcu, mh, mw, bpm = jpeg_geometry(image.shape[:2], subsampling)
+    px = np.pad(image.astype(np.int64),
+                ((0, mh * mcu - image.shape[0]), (0, mw * mcu - image.shape[1]), (0, 0)), "edge")
+    r, g, b = px[..., 0], px[..., 1], px[..., 2]
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    if subsampling == "420":
+        cb, cr = ((c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + 2) >> 2
+                  for c in (cb, cr))
+
+    def blocks(p):  # [R, C] -> [R / 8, C / 8, 8, 8]
+        return p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).transpose(0, 2, 1, 3)
+
+    yb, cbb, crb = blocks(y - 128), blocks(cb - 128), blocks(cr - 128)
+    if subsampling == "420":
+        yb = yb.reshape(mh, 2, mw, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(mh, mw, 4, 8, 8)
+    else:
+        yb = yb[:, :, None]
+    scan = np.concatenate([yb, cbb[:, :, None], crb[:, :, None]], axis=2)  # [mh, mw, bpm, 8, 8]
+    c = _jpeg_dct_pass(scan, True)                                         # rows
+    c = _jpeg_dct_pass(c.swapaxes(-1, -2), False).swapaxes(-1, -2)         # columns
+    q = np.asarray(qtabs, np.int64).reshape(2, 8, 8)
+    qsel = np.stack([q[0]] * (bpm - 2) + [q[1], q[1]])
+    v = np.sign(c) * ((np.abs(c) + 4 * qsel) // (8 * qsel))
+    v = v.reshape(mh, mw * bpm, 64)
+    v[..., 0] = np.clip(v[..., 0], -1024, 1024)
+    v[..., 1:] = np.clip(v[..., 1:], -1023, 1023)
+    return v[..., list(JPEG_ZIGZAG)].astype(np.int16)
+
+
+def jpeg_scan(coef: np.ndarray, subsampling: str, stats=None):
+    """Entropy-code int16 [intervals, blocks, 64] zigzag coefficients: one byte string per
+    restart interval (DC prediction from 0, Huffman codes MSB first, padded with 1-bits to a
+    byte, FF stuffed as FF 00).  ``stats``: a dict whose counters are advanced."""
+    huff = jpeg_huff_codes().tolist()
+    comp = (0, 0, 0, 0, 1, 2) if subsampling == "420" else (0, 1, 2)
+    bpm = len(comp)
+    segs = []
+    for row in coef.tolist():
+        acc, nbits = 0, 0
+        pred = [0, 0, 0]
+        for i, blk in enumerate(row):
+            c = comp[i % bpm]
+            dc, ac = huff[min(c, 1)], huff[2 + min(c, 1)]
+            diff = blk[0] - pred[c]
+            pred[c] = blk[0]
+            s = abs(diff).bit_length()
+            e = dc[s]
+            acc = (((acc << (e >> 16)) | (e & 0xffff)) << s) | ((diff if diff >= 0 else diff - 1)
+                                                                & ((1 << s) - 1))
+            nbits += (e >> 16) + s
+            if stats is not None:
+                stats["max_dc_cat"] = max(stats["max_dc_cat"], s)
+                stats["dc_nonzero"] += diff != 0
+            run = 0
+            for k in range(1, 64):
+                v = blk[k]
+                if v == 0:
+                    run += 1
+                    continue
+                while run > 15:
+                    e = ac[0xf0]
+                    acc = (acc << (e >> 16)) | (e & 0xffff)
+                    nbits += e >> 16
+                    run -= 16
+                    if stats is not None:
+                        stats["zrl"] += 1
+                s = abs(v).bit_length()
+                e = ac[(run << 4) | s]
+                acc = (((acc << (e >> 16)) | (e & 0xffff)) << s) | ((v if v >= 0 else v - 1)
+                                                                    & ((1 << s) - 1))
+                nbits += (e >> 16) + s
+                run = 0
+                if stats is not None:
+                    stats["max_ac_cat"] = max(stats["max_ac_cat"], s)
+            if run:
+                e = ac[0x00]
+                acc = (acc << (e >> 16)) | (e & 0xffff)
+                nbits += e >> 16
+                if stats is not None:
+                    stats["eob"] += 1
+        fill = -nbits % 8
+        if stats is not None:
+            stats["bits"] += nbits
+        raw = ((acc << fill) | ((1 << fill) - 1)).to_bytes((nbits + fill) // 8, "big")
+        if stats is not None:
+            stats["stuffed"] += raw.count(b"\xff")
+        segs.append(raw.replace(b"\xff", b"\xff\x00"))
+    return segs
+
+
+def jpeg_encode(images, subsampling: str = "420", quality: int = 75, stats: bool = False,
+                qtabs=None, header=None):
+    """Baseline JPEG files of uint8 [M, H, W, 3] RGB images: THE definition the HIP kernels
+    (csrc/kernels/jpeg_encode.hip) equal byte for byte.  Returns a list of M ``bytes``; with
+    ``stats`` also a list of M dicts counting stuffed bytes, ZRL symbols, EOBs, nonzero DC
+    differences, the largest DC / AC categories and the scan's bits before padding.  ``qtabs`` int [2, 64] (natural order) and
+    ``header`` (bytes) override the tables and header that ``quality`` gives -- the encoder's
+    device copies on the CPU path.
+
+    File: header (jpeg_header), then one interleaved scan with a restart interval of one MCU
+    row: interval i > 0 is preceded by RST((i - 1) % 8); EOI.  No JFIF / EXIF segment."""
+    arr = images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images)
+    if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
+        raise ValueError(f"images are uint8 [M, H, W, 3], got {arr.dtype} {arr.shape}")
+    if qtabs is None:
+        qtabs = jpeg_quant_tables(quality)
+    if header is None:
+        header = jpeg_header(arr.shape[1:3], subsampling, qtabs)
+    files, counts = [], []
+    for img in arr:
+        st = dict(stuffed=0, zrl=0, eob=0, dc_nonzero=0, max_dc_cat=0, max_ac_cat=0, bits=0)
+        segs = jpeg_scan(jpeg_coefficients(img, subsampling, qtabs), subsampling, st)
+        out = bytearray(header)
+        for i, s in enumerate(segs):
+            if i:
+                out += bytes([0xff, 0xd0 + ((i - 1) & 7)])
+            out += s
+        out += b"\xff\xd9"
+        files.append(bytes(out))
+        counts.append(st)
+    return (files, counts) if stats else files
