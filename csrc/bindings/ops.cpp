@@ -1016,6 +1016,73 @@ void jpeg_encode(const at::Tensor& images, const at::Tensor& qtab, const at::Ten
   TORCH_CHECK(rc == 0, "kvedge: jpeg_encode failed rc=", rc);
 }
 
+// K22: snapshot annotation (csrc/kernels/annotate.hip).  images uint8 [N,H,W,3], drawn in
+// place; table int32 [S,168] and font int32 [88] belong to an ops.AnnotateStyle; det / count /
+// track_id are optional (no det: only the privacy polygons); batch row n is camera slot0 + n.
+void annotate(at::Tensor& images, const at::Tensor& table, const at::Tensor& font,
+              const c10::optional<at::Tensor>& det, const c10::optional<at::Tensor>& count,
+              const c10::optional<at::Tensor>& track_id, int64_t Hs, int64_t Ws, int64_t slot0) {
+  check_dev(images, "images");
+  check_dev(table, "table");
+  check_dev(font, "font");
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3,
+              "kvedge: annotate images uint8 [N,H,W,3]");
+  const int64_t N = images.size(0), H = images.size(1), W = images.size(2);
+  TORCH_CHECK(H >= 1 && H <= 8192 && W >= 4 && W <= 8192 && W % 4 == 0,
+              "kvedge: annotate image size 1..8192 x 4..8192 with W % 4 == 0, got ", H, "x", W);
+  TORCH_CHECK(Hs >= 1 && Hs <= 4096 && Ws >= 1 && Ws <= 4096,
+              "kvedge: annotate source frame 1..4096, got ", Hs, "x", Ws);
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 &&
+                  table.size(1) == kv_annotate_table_stride(),
+              "kvedge: annotate table int32 [S, ", kv_annotate_table_stride(), "]");
+  const int64_t S = table.size(0);
+  TORCH_CHECK(font.scalar_type() == at::kInt && font.numel() == kv_annotate_font_words(),
+              "kvedge: annotate font int32 [", kv_annotate_font_words(), "]");
+  TORCH_CHECK(S < (1ll << 24) && N <= 65535, "kvedge: annotate too many images");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: annotate cameras [", slot0, ", ", slot0 + N,
+              ") outside the style's ", S);
+  TORCH_CHECK(images.device() == table.device() && images.device() == font.device(),
+              "kvedge: annotate operands on different devices");
+  int64_t max_det = 0;
+  const float* det_p = nullptr;
+  const int* count_p = nullptr;
+  const int* tid_p = nullptr;
+  if (det.has_value()) {
+    check_dev(*det, "det");
+    TORCH_CHECK(det->scalar_type() == at::kFloat && det->dim() == 3 && det->size(0) == N &&
+                    det->size(2) == 6, "kvedge: annotate det fp32 [N,max_det,6]");
+    max_det = det->size(1);
+    TORCH_CHECK(max_det >= 1 && max_det <= 300, "kvedge: annotate max_det is 1..300, got ",
+                max_det);
+    TORCH_CHECK(count.has_value(), "kvedge: annotate det needs count");
+    check_dev(*count, "count");
+    TORCH_CHECK(count->scalar_type() == at::kInt && count->dim() == 1 && count->size(0) == N,
+                "kvedge: annotate count int32 [N]");
+    TORCH_CHECK(det->device() == images.device() && count->device() == images.device(),
+                "kvedge: annotate operands on different devices");
+    det_p = det->data_ptr<float>();
+    count_p = count->data_ptr<int>();
+    if (track_id.has_value()) {
+      check_dev(*track_id, "track_id");
+      TORCH_CHECK(track_id->scalar_type() == at::kInt && track_id->dim() == 2 &&
+                      track_id->size(0) == N && track_id->size(1) == max_det,
+                  "kvedge: annotate track_id int32 [N,max_det]");
+      TORCH_CHECK(track_id->device() == images.device(),
+                  "kvedge: annotate operands on different devices");
+      tid_p = track_id->data_ptr<int>();
+    }
+  } else {
+    TORCH_CHECK(!count.has_value() && !track_id.has_value(),
+                "kvedge: annotate count and track_id come with det");
+  }
+  const c10::DeviceGuard g(images.device());
+  const int rc = kv_annotate(images.data_ptr<uint8_t>(), table.data_ptr<int>(),
+                             font.data_ptr<int>(), det_p, count_p, tid_p, (int)N, (int)S,
+                             (int)slot0, (int)H, (int)W, (int)Hs, (int)Ws, (int)max_det,
+                             cur_stream(images));
+  TORCH_CHECK(rc == 0, "kvedge: annotate failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -1145,6 +1212,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("jpeg_encode(Tensor images, Tensor qtab, Tensor huff, Tensor header, Tensor(a!) coef, "
         "Tensor(b!) scratch, Tensor(c!) seglen, Tensor(d!) out, Tensor(e!) length, bool sub420) "
         "-> ()");
+  m.def("annotate(Tensor(a!) images, Tensor table, Tensor font, Tensor? det, Tensor? count, "
+        "Tensor? track_id, int Hs, int Ws, int slot0) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1193,6 +1262,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("zone_update", zone_update);
   m.impl("frame_watch", frame_watch);
   m.impl("jpeg_encode", jpeg_encode);
+  m.impl("annotate", annotate);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

@@ -251,6 +251,21 @@ int kv_jpeg_encode(const unsigned char* images, const int* qtab, const int* huff
                    const unsigned char* header, short* coef, unsigned char* scratch, int* seglen,
                    unsigned char* out, int* length, int M, int H, int W, int sub420,
                    long long cap, hipStream_t s);
+// K22 (annotate.hip): boxes, labels and the privacy mosaic drawn into images uint8 RGB
+// [N,H,W,3] in place, one launch.  table int32 [S, kv_annotate_table_stride()] (image n uses
+// row slot0 + n) and font int32 [kv_annotate_font_words()] are read from device memory at run
+// time, every word clamped.  det fp32 [N,max_det,6] / count int32 [N] / track_id int32
+// [N,max_det] in an (Hs, Ws) pixel frame; det == nullptr (then count and track_id too): only
+// the polygons apply; track_id == nullptr: every id is -1.  Byte-identical to
+// ops.reference.annotate; the rules and the layout are at the top of annotate.hip.
+// Returns -1 H outside 1..8192 or W outside 4..8192 or W % 4, -2 N outside 0..65535 or
+// slot0 + N > S, -3 max_det outside 1..300, -4 Hs or Ws outside 1..4096, -5 count missing (or
+// given without det), -7 misaligned operand.  N == 0 launches nothing.
+int kv_annotate_table_stride(void);
+int kv_annotate_font_words(void);
+int kv_annotate(unsigned char* images, const int* table, const int* font, const float* det,
+                const int* count, const int* track_id, int N, int S, int slot0, int H, int W,
+                int Hs, int Ws, int max_det, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

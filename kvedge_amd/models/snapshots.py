@@ -11,6 +11,11 @@ inside the captured graph, no host in the loop.  The encoder's tables and worksp
 (ops.JpegEncoder) are allocated here, outside the graph's pool; ``set_quality`` rewrites the
 tables in place, so a captured step encodes at the new quality from its next replay.
 
+With ``annotate`` (an ops.AnnotateStyle) one more launch between the two draws what the device
+knows into the thumbnail before it is encoded (ops.annotate, csrc/kernels/annotate.hip): the
+boxes of a detector with their ``cls:id`` labels, and a mosaic over boxes of privacy classes
+and over fixed privacy polygons.  The style's setters take effect from the next replay too.
+
 A ``KvWatched`` goes around this wrapper, not inside it: the watch stays the outermost stage
 and its two outputs the last two.
 """
@@ -21,6 +26,7 @@ from typing import List, Optional
 import torch
 
 from .. import ops
+from .tracking import KvTracked
 
 
 class KvSnapshots:
@@ -29,12 +35,16 @@ class KvSnapshots:
     frames the engine serves from (InferenceEngine ``frame_hw``); None = model-size frames.
     ``width``: thumbnail width; the height follows the frame's shape (ops.thumbnail_plan).
     ``cap``: bytes per output row (default and upper limit: ops.jpeg_max_bytes of the
-    thumbnail, the derived worst case); a file that does not fit gives ``snap_len = -size``."""
+    thumbnail, the derived worst case); a file that does not fit gives ``snap_len = -size``.
+    ``annotate``: an ops.AnnotateStyle for ``streams`` cameras, in the pixel frame the boxes are
+    reported in (frame pixels when the engine has a frame size, model pixels otherwise); None
+    = bare pictures, exactly the launches and bytes of a stage without it."""
 
     stateful = True  # InferenceEngine passes slot0 = first batch row of the slice
 
     def __init__(self, inner, streams: int, frame_hw=None, width: int = 320,
-                 subsampling: str = "420", quality: int = 75, cap: Optional[int] = None):
+                 subsampling: str = "420", quality: int = 75, cap: Optional[int] = None,
+                 annotate: Optional["ops.AnnotateStyle"] = None):
         self.inner = inner
         self.device = inner.device
         self.image_size = getattr(inner, "image_size", 224)
@@ -49,6 +59,21 @@ class KvSnapshots:
         self.cap = min(int(cap), self.encoder.max_bytes) if cap else self.encoder.max_bytes
         self.snap_index = None  # set by the first step
         self._inner_stateful = bool(getattr(inner, "stateful", False))
+        if annotate is not None:
+            if not isinstance(annotate, ops.AnnotateStyle):
+                raise TypeError("annotate must be an ops.AnnotateStyle, got "
+                                f"{type(annotate).__name__}")
+            if (annotate.streams != self.streams
+                    or annotate.device.type != torch.device(self.device).type):
+                raise ValueError(f"the style covers {annotate.streams} cameras on "
+                                 f"{annotate.device}, the stage {self.streams} on {self.device}")
+        self.annotate = annotate
+        self._tracked = None  # the KvTracked stage inside, whose track_index finds track_id
+        m = inner
+        while m is not None and self._tracked is None:
+            if isinstance(m, KvTracked):
+                self._tracked = m
+            m = getattr(m, "__dict__", {}).get("inner")
 
     def _for(self, hw):
         if hw not in self._by_hw:
@@ -102,11 +127,25 @@ class KvSnapshots:
         small = ops.frame_resize(src, plan, out=ops.empty(n, *plan.dst_hw, 3, dtype=torch.uint8,
                                                           device=src.device),
                                  src_format=src_format)
+        if self.annotate is not None:
+            ops.annotate(small, self.annotate, *self._boxes(out, n), src_hw=hw, slot0=slot0)
         buf = ops.empty(n, min(self.cap, enc.max_bytes), dtype=torch.uint8, device=src.device)
         length = ops.empty(n, dtype=torch.int32, device=src.device)
         ops.jpeg_encode(small, enc, out=buf, lengths=length, slot0=slot0)
         self.snap_index = len(out)
         return (*out, buf, length)
+
+    def _boxes(self, out, n: int):
+        """(det, count, track_id) among the inner outputs: the first two of a detector, and
+        the tracker's ids where it recorded them; (None, None, None) for a classifier."""
+        if not (len(out) >= 2 and out[0].dtype == torch.float32 and out[0].dim() == 3
+                and out[0].shape[0] == n and out[0].shape[2] == 6
+                and out[1].dtype == torch.int32 and tuple(out[1].shape) == (n,)):
+            return None, None, None
+        tid = None
+        if self._tracked is not None and self._tracked.track_index is not None:
+            tid = out[self._tracked.track_index]
+        return out[0], out[1], tid
 
     def __call__(self, frames_u8: torch.Tensor, slot0: int = 0):
         """Model-size frames: the picture is the model's own input, resized."""

@@ -23,7 +23,8 @@ from .. import ops
 
 
 class KvTracked:
-    """inner outputs ``(det, count, ...)`` -> ``(det, count, ..., track_id)``.  Tracking runs
+    """inner outputs ``(det, count, ...)`` -> ``(det, count, ..., track_id)``; ``track_index``
+    is the position of ``track_id`` in them.  Tracking runs
     on the boxes as they are reported: frame pixels when the engine has a frame size
     (``from_source``), model pixels otherwise."""
 
@@ -43,6 +44,7 @@ class KvTracked:
             raise ValueError(f"min_hits {min_hits} outside 1..255")
         self.state = ops.TrackState(streams, max_tracks, self.device)
         self.image_size = getattr(inner, "image_size", 640)
+        self.track_index = None  # position of track_id in the outputs, set by the first step
 
     # -- what the engine, the autotuner and the module read off a model
     def convs(self) -> List:
@@ -63,6 +65,7 @@ class KvTracked:
         tid = ops.track_update(det, count, self.state, slot0=slot0, iou=self.iou,
                                max_age=self.max_age, min_hits=self.min_hits,
                                class_aware=self.class_aware)
+        self.track_index = len(out)
         return (*out, tid)
 
     def __call__(self, frames_u8: torch.Tensor, slot0: int = 0):

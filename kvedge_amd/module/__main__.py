@@ -139,6 +139,17 @@ def main(argv=None):
                     help="seconds between periodic pictures per camera (0 = never)")
     ap.add_argument("--snapshot-max-bytes", type=int, default=d.snapshot_max_bytes,
                     help="a larger picture is counted as oversize, not sent")
+    ap.add_argument("--snapshot-annotate", action="store_true",
+                    help="--snapshots: draw boxes, cls:id labels and the privacy mosaic into "
+                         "the pictures on the device (messages gain `annotated`)")
+    ap.add_argument("--snapshot-labels", default=d.snapshot_labels,
+                    choices=["none", "class", "id", "both"],
+                    help="label parts of an annotated box (changes without a rebuild)")
+    ap.add_argument("--privacy-classes", default="",
+                    help="class ids whose boxes are hidden under a mosaic, e.g. 0,2 (at most 8)")
+    ap.add_argument("--privacy-zones-json", default="",
+                    help="polygons hidden under a mosaic, inline JSON '[{\"name\": ..., "
+                         "\"polygon\": [[x, y], ...], \"cameras\"?}]' (at most 8, 3..8 vertices)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -189,7 +200,11 @@ def main(argv=None):
                        snapshot_subsampling=a.snapshot_subsampling,
                        snapshot_quality=a.snapshot_quality,
                        snapshot_every_s=a.snapshot_every_s,
-                       snapshot_max_bytes=a.snapshot_max_bytes).validate()
+                       snapshot_max_bytes=a.snapshot_max_bytes,
+                       snapshot_annotate=a.snapshot_annotate,
+                       snapshot_labels=a.snapshot_labels,
+                       snapshot_privacy_classes=a.privacy_classes,
+                       snapshot_privacy_zones=a.privacy_zones_json).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -447,10 +447,15 @@ class ModuleApp:
             # inside the watch, so that the watch's two outputs stay the last two; a device
             # row holds the derived worst case up to 1 MiB (a larger file is reported by size)
             size = cfg.resolved_image_size()
+            style = None
+            if cfg.snapshot_annotate:  # boxes, labels and the privacy mosaic in the pictures
+                from .snapshots import build_annotate_style
+
+                style = build_annotate_style(cfg, dev)
             self.model = KvSnapshots(self.model, cfg.batch, frame_hw=cfg.frame_hw() or (size, size),
                                      width=cfg.snapshot_width,
                                      subsampling=cfg.snapshot_subsampling,
-                                     quality=cfg.snapshot_quality, cap=1 << 20)
+                                     quality=cfg.snapshot_quality, cap=1 << 20, annotate=style)
         if cfg.watch:
             from ..models.watching import KvWatched
 
@@ -835,6 +840,14 @@ class ModuleApp:
                 and self.cfg.snapshot_quality != old.snapshot_quality):
             # the quantisation tables live in device memory, like the watch thresholds
             self.snapshots.stage.set_quality(self.cfg.snapshot_quality)
+        if (self.snapshots is not None and self.snapshots.stage.annotate is not None
+                and not self.cfg.needs_rebuild(old)
+                and any(getattr(self.cfg, k) != getattr(old, k)
+                        for k in ModuleConfig.ANNOTATE_LIVE_KEYS)):
+            # so does the annotate style: no rebuild, no recapture
+            from .snapshots import apply_annotate_style
+
+            apply_annotate_style(self.snapshots.stage.annotate, self.cfg)
         if self.cfg.needs_rebuild(old):
             self.state["rebuilds"] += 1
             log_event(self.log, "rebuild", model=self.cfg.model, batch=self.cfg.batch)

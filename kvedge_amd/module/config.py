@@ -18,6 +18,8 @@ DTYPES = ("bf16",)
 ZONE_ANCHORS = ("bottom", "centre")
 MAX_REGIONS = 8  # lines, and zones, per camera (csrc/kernels/zones.hip)
 SNAPSHOT_SUBSAMPLINGS = ("420", "444")
+SNAPSHOT_LABELS = ("none", "class", "id", "both")
+MAX_PRIVACY = 8  # privacy classes, and privacy zones, per camera (csrc/kernels/annotate.hip)
 
 
 def _point(p, what: str):
@@ -62,6 +64,36 @@ def _regions(v, kind: str) -> Tuple[Dict[str, Any], ...]:
             n["polygon"] = [_point(p, f"{kind}[{i}].polygon[{j}]") for j, p in enumerate(poly)]
         out.append(n)
     return tuple(out)
+
+
+def _privacy_zones(v) -> Tuple[Dict[str, Any], ...]:
+    """The ``snapshot_privacy_zones`` twin key, shaped like ``zones`` without a class: name,
+    polygon, cameras (None = all), in normal form."""
+    if isinstance(v, str):
+        v = json.loads(v) if v.strip() else []
+    if isinstance(v, (list, tuple)):
+        for i, r in enumerate(v):
+            if isinstance(r, dict) and "class" in r:
+                raise ValueError(f"snapshot_privacy_zones[{i}]: unknown keys ['class']")
+    return tuple({k: r[k] for k in ("name", "cameras", "polygon")}
+                 for r in _regions(v, "snapshot_privacy_zones"))
+
+
+def _int_tuple(v, what: str) -> Tuple[int, ...]:
+    """A list of integers, or the same as "0,2" / JSON text."""
+    if isinstance(v, str):
+        v = [p for p in v.replace("[", " ").replace("]", " ").replace(",", " ").split()]
+    if v is None:
+        v = []
+    if isinstance(v, bool) or not isinstance(v, (list, tuple)):
+        raise ValueError(f"{what} must be a list of integers, got {v!r}")
+    try:
+        out = tuple(int(c) for c in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a list of integers, got {v!r}") from None
+    if any(isinstance(c, (bool, float)) and int(c) != c for c in v):
+        raise ValueError(f"{what} must be a list of integers, got {v!r}")
+    return out
 
 
 @dataclass(frozen=True)
@@ -145,6 +177,23 @@ class ModuleConfig:
     snapshot_quality: int = 75
     snapshot_every_s: float = 0.0
     snapshot_max_bytes: int = 131072
+    # snapshot_annotate: what the device knows is drawn into each picture before it is encoded
+    # (ops.annotate) -- with a detector the boxes (snapshot_boxes, outlines of
+    # snapshot_box_thickness 1..4 pixels) and their labels (snapshot_labels "class" / "id" /
+    # "both" = cls:id / "none", glyphs at snapshot_label_scale 1..2); boxes of
+    # snapshot_privacy_classes (at most 8 class ids) and the polygons snapshot_privacy_zones
+    # ([{name, polygon: [[x, y], ...] (3..8 vertices), cameras?}], at most 8, in the pixel frame
+    # the boxes are reported in) are hidden under a mosaic of snapshot_privacy_block (4 / 8 /
+    # 16) thumbnail pixels.  Only snapshot_annotate needs a rebuild: the others are read on
+    # the device at every step
+    snapshot_annotate: bool = False
+    snapshot_boxes: bool = True
+    snapshot_labels: str = "both"
+    snapshot_box_thickness: int = 1
+    snapshot_label_scale: int = 1
+    snapshot_privacy_classes: Tuple[int, ...] = ()
+    snapshot_privacy_block: int = 8
+    snapshot_privacy_zones: Tuple[Dict[str, Any], ...] = ()
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -166,11 +215,16 @@ class ModuleConfig:
                "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
                "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
-               "watch_bg_shift", "snapshots", "snapshot_width", "snapshot_subsampling")
+               "watch_bg_shift", "snapshots", "snapshot_width", "snapshot_subsampling",
+               "snapshot_annotate")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
             object.__setattr__(self, kind, _regions(getattr(self, kind), kind))
+        object.__setattr__(self, "snapshot_privacy_zones",
+                           _privacy_zones(self.snapshot_privacy_zones))
+        object.__setattr__(self, "snapshot_privacy_classes",
+                           _int_tuple(self.snapshot_privacy_classes, "snapshot_privacy_classes"))
 
     def validate(self) -> "ModuleConfig":
         if self.model not in MODELS:
@@ -271,6 +325,43 @@ class ModuleConfig:
             raise ValueError("snapshot_max_bytes must be >= 1")
         if self.snapshots and self.model == "simulated-temperature":
             raise ValueError("snapshots need frames: a vision model")
+        # the annotate style's ranges (ops.AnnotateStyle, csrc/kernels/annotate.hip)
+        if self.snapshot_labels not in SNAPSHOT_LABELS:
+            raise ValueError(f"snapshot_labels must be one of {SNAPSHOT_LABELS}, got "
+                             f"{self.snapshot_labels!r}")
+        if not 1 <= self.snapshot_box_thickness <= 4:
+            raise ValueError("snapshot_box_thickness must be 1..4")
+        if not 1 <= self.snapshot_label_scale <= 2:
+            raise ValueError("snapshot_label_scale must be 1..2")
+        if self.snapshot_privacy_block not in (4, 8, 16):
+            raise ValueError("snapshot_privacy_block must be 4, 8 or 16")
+        if len(self.snapshot_privacy_classes) > MAX_PRIVACY:
+            raise ValueError(f"at most {MAX_PRIVACY} snapshot_privacy_classes, got "
+                             f"{len(self.snapshot_privacy_classes)}")
+        if not all(0 <= c <= 65535 for c in self.snapshot_privacy_classes):
+            raise ValueError("snapshot_privacy_classes must be class ids 0..65535")
+        pz = self.snapshot_privacy_zones
+        if len(pz) > MAX_PRIVACY:
+            raise ValueError(f"at most {MAX_PRIVACY} snapshot_privacy_zones, got {len(pz)}")
+        if len({r["name"] for r in pz}) != len(pz):
+            raise ValueError("snapshot_privacy_zones names must be unique, got "
+                             f"{[r['name'] for r in pz]}")
+        for r in pz:
+            if r["cameras"] is not None and not all(0 <= c < self.batch for c in r["cameras"]):
+                raise ValueError(f"privacy zone {r['name']!r}: cameras must be 0..batch - 1")
+            if not 3 <= len(r["polygon"]) <= 8:
+                raise ValueError(f"privacy zone {r['name']!r} needs 3..8 vertices, got "
+                                 f"{len(r['polygon'])}")
+        if self.snapshot_annotate:  # cross-key limits bind only when the stage is on
+            if not self.snapshots:
+                raise ValueError("snapshot_annotate draws into the snapshots: it needs "
+                                 "snapshots true")
+            base = ModuleConfig.__dataclass_fields__
+            if self.model not in ("yolov8n", "detect-classify"):
+                for k in self.ANNOTATE_BOX_KEYS:
+                    if getattr(self, k) != base[k].default:
+                        raise ValueError(f"{k} needs a detector: model {self.model} has no "
+                                         f"boxes (snapshot_privacy_zones work with any model)")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -294,6 +385,10 @@ class ModuleConfig:
                 v = int(v)
             elif isinstance(cur, float):
                 v = float(v)
+            elif k == "snapshot_privacy_zones":
+                v = _privacy_zones(v)
+            elif k == "snapshot_privacy_classes":
+                v = _int_tuple(v, k)
             elif isinstance(cur, tuple):
                 v = _regions(v, k)
             else:
@@ -329,6 +424,12 @@ class ModuleConfig:
 
     SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
                      "snapshot_every_s", "snapshot_max_bytes")
+
+    # the annotate stage: what needs boxes, and what the device reads live
+    ANNOTATE_BOX_KEYS = ("snapshot_boxes", "snapshot_labels", "snapshot_box_thickness",
+                         "snapshot_label_scale", "snapshot_privacy_classes")
+    ANNOTATE_LIVE_KEYS = ANNOTATE_BOX_KEYS + ("snapshot_privacy_block", "snapshot_privacy_zones")
+    ANNOTATE_KEYS = ("snapshot_annotate",) + ANNOTATE_LIVE_KEYS
 
     def watch_params(self) -> Dict[str, int]:
         """The threshold words of ops.WatchState.set_params: levels in 1/16 luma
@@ -367,4 +468,11 @@ class ModuleConfig:
         if all(getattr(self, k) == getattr(base, k) for k in self.SNAPSHOT_KEYS):
             for k in self.SNAPSHOT_KEYS:
                 d.pop(k)
+        # and the annotate keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.ANNOTATE_KEYS):
+            for k in self.ANNOTATE_KEYS:
+                d.pop(k)
+        else:
+            d["snapshot_privacy_classes"] = list(d["snapshot_privacy_classes"])
+            d["snapshot_privacy_zones"] = list(d["snapshot_privacy_zones"])
         return d

@@ -3,7 +3,11 @@
 Every step only the ``snap_len`` row (4 bytes per camera) comes to the host; the bytes of a
 picture are copied only for a camera that sends one -- when one of its watch alarms was raised
 in this step (``alarm:<condition>``, read off module.watch.CameraTotals) or its periodic timer
-ran out (``periodic``) -- or when direct method ``snapshot`` asks for it."""
+ran out (``periodic``) -- or when direct method ``snapshot`` asks for it.
+
+With ``snapshot_annotate`` the pictures carry the boxes, labels and the privacy mosaic
+(ops.annotate); the twin's style keys become an ops.AnnotateStyle here, and are written into
+it again whenever one of them changes."""
 from __future__ import annotations
 
 import base64
@@ -11,6 +15,24 @@ from typing import Any, Dict, List, Optional, Tuple
 
 from .. import ops
 from ..models.snapshots import snapshots_of
+
+
+def apply_annotate_style(style: "ops.AnnotateStyle", cfg) -> "ops.AnnotateStyle":
+    """Write the twin's snapshot_* style keys into ``style`` (device memory: the captured step
+    reads it at every replay).  Privacy zone i of the config is polygon i on the cameras it
+    names (all by default)."""
+    style.set_boxes(cfg.snapshot_boxes).set_labels(cfg.snapshot_labels)
+    style.set_thickness(cfg.snapshot_box_thickness).set_label_scale(cfg.snapshot_label_scale)
+    style.set_privacy_classes(cfg.snapshot_privacy_classes)
+    style.set_privacy_block(cfg.snapshot_privacy_block).clear_privacy_polygons()
+    for i, r in enumerate(cfg.snapshot_privacy_zones):
+        for cam in (r["cameras"] if r["cameras"] is not None else [None]):
+            style.set_privacy_polygon(i, r["polygon"], camera=cam)
+    return style
+
+
+def build_annotate_style(cfg, device) -> "ops.AnnotateStyle":
+    return apply_annotate_style(ops.AnnotateStyle(cfg.batch, device), cfg)
 
 
 class SnapshotSender:
@@ -29,8 +51,11 @@ class SnapshotSender:
 
     def message(self, outputs, camera: int, length: int) -> Dict[str, Any]:
         h, w = self.stage.thumb_hw
-        return {"camera": camera, "width": w, "height": h, "bytes": length,
-                "jpeg_b64": base64.b64encode(self._picture(outputs, camera, length)).decode()}
+        msg = {"camera": camera, "width": w, "height": h, "bytes": length,
+               "jpeg_b64": base64.b64encode(self._picture(outputs, camera, length)).decode()}
+        if self.stage.annotate is not None:
+            msg["annotated"] = True
+        return msg
 
     def due(self, totals, now: float, every_s: float) -> List[Tuple[int, str]]:
         """(camera, reason) of every picture this step owes.  ``totals``: an updated
@@ -62,8 +87,11 @@ class SnapshotSender:
                 self.oversize += 1
                 continue
             msg = self.message(outputs, cam, n)
-            send({"camera": cam, "reason": reason, "step": step, "width": msg["width"],
-                  "height": msg["height"], "bytes": n, "jpeg_b64": msg["jpeg_b64"]})
+            out = {"camera": cam, "reason": reason, "step": step, "width": msg["width"],
+                   "height": msg["height"], "bytes": n, "jpeg_b64": msg["jpeg_b64"]}
+            if "annotated" in msg:
+                out["annotated"] = True
+            send(out)
             self.sent += 1
 
     def method(self, outputs, payload, max_bytes: int) -> Tuple[int, Dict[str, Any]]:

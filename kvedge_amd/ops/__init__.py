@@ -1573,6 +1573,231 @@ def jpeg_encode(images: torch.Tensor, enc: JpegEncoder, out: Optional[torch.Tens
     return out, lengths
 
 
+# ---------------------------------------------------------------------------
+# snapshot annotation: boxes, labels and a privacy mosaic drawn into the thumbnails
+# ---------------------------------------------------------------------------
+ANNOTATE_TABLE_STRIDE = _ref.ANN_TABLE_STRIDE
+ANNOTATE_MAX_CLASSES = ANNOTATE_MAX_POLYGONS = ANNOTATE_MAX_VERTICES = _ref.ANN_MAX
+ANNOTATE_LABELS = {"none": 0, "class": 1, "id": 2, "both": 3}
+ANNOTATE_COLOUR_BY = {"class": 0, "track": 1}
+ANNOTATE_BLOCKS = (4, 8, 16)
+ANNOTATE_MAX_SRC = _ref.ANN_MAX_SRC
+# sixteen colours that stay apart on a thumbnail, (R, G, B)
+ANNOTATE_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200),
+                    (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+                    (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255),
+                    (170, 110, 40), (255, 250, 200), (128, 0, 0), (170, 255, 195))
+
+
+class AnnotateStyle:
+    """How the snapshots of ``streams`` cameras are drawn: one int32 table ``table``
+    [streams, 168] on ``device`` (the layout csrc/kernels/annotate.hip reads), its host mirror
+    ``host`` and named views: ``boxes`` ``labels`` ``colour_by`` ``thickness`` ``scale``
+    ``block`` ``max_draw`` ``n_polygons`` [S], ``privacy_classes`` [S, 8] (-1 = unused),
+    ``n_vertex`` [S, 8], ``vertex`` [S, 8, 8, 2] (given in pixels of the frame the boxes live
+    in, stored in the tracker's quarter pixels) and ``palette`` [S, 16] (R | G << 8 | B << 16);
+    plus one font table ``font`` int32 [88] for all of them (5 x 7 glyphs of ``0-9`` and ``:``).
+    ``camera=None`` in a setter means every camera.  The kernel reads the tables at run time:
+    a setter takes effect from the next call, or the next replay of a captured step."""
+
+    def __init__(self, streams: int, device="cpu"):
+        if isinstance(streams, bool) or int(streams) < 1:
+            raise ValueError(f"streams must be >= 1, got {streams!r}")
+        self.streams = int(streams)
+        dev = torch.device(device)
+        self.host = torch.zeros(self.streams, ANNOTATE_TABLE_STRIDE, dtype=torch.int32)
+        self.font_host = torch.from_numpy(_ref.annotate_font())
+        self.table = self.host if dev.type == "cpu" else self.host.to(dev)
+        self.font = self.font_host if dev.type == "cpu" else self.font_host.to(dev)
+        for name, v in self._views(self.table).items():
+            setattr(self, name, v)
+        h = self._views(self.host)
+        h["boxes"].fill_(1)
+        h["labels"].fill_(ANNOTATE_LABELS["both"])
+        h["thickness"].fill_(1)
+        h["scale"].fill_(1)
+        h["block"].fill_(8)
+        h["max_draw"].fill_(32)
+        h["privacy_classes"].fill_(-1)
+        h["palette"].copy_(torch.tensor([r | g << 8 | b << 16 for r, g, b in ANNOTATE_PALETTE],
+                                        dtype=torch.int32))
+        self._push()
+
+    @staticmethod
+    def _views(tab: torch.Tensor) -> dict:
+        r = _ref
+        return {"boxes": tab[:, r.ANN_BOXES], "labels": tab[:, r.ANN_LABELS],
+                "colour_by": tab[:, r.ANN_COLOUR_BY], "thickness": tab[:, r.ANN_THICKNESS],
+                "scale": tab[:, r.ANN_SCALE], "block": tab[:, r.ANN_BLOCK],
+                "max_draw": tab[:, r.ANN_MAX_DRAW], "n_polygons": tab[:, r.ANN_N_POLY],
+                "privacy_classes": tab[:, r.ANN_PRIV_CLS:r.ANN_PRIV_CLS + 8],
+                "n_vertex": tab[:, r.ANN_N_VERT:r.ANN_N_VERT + 8],
+                "vertex": tab[:, r.ANN_VERT:r.ANN_VERT + 128].unflatten(1, (8, 8, 2)),
+                "palette": tab[:, r.ANN_PALETTE:r.ANN_PALETTE + 16]}
+
+    @property
+    def device(self) -> torch.device:
+        return self.table.device
+
+    def _push(self) -> None:
+        if self.table is not self.host:
+            self.table.copy_(self.host)
+
+    def _rows(self, camera):
+        if camera is None:
+            return slice(None)
+        if isinstance(camera, bool) or not 0 <= int(camera) < self.streams:
+            raise ValueError(f"camera {camera} outside 0..{self.streams - 1}")
+        return slice(int(camera), int(camera) + 1)
+
+    def _set(self, camera, name: str, value) -> "AnnotateStyle":
+        self._views(self.host)[name][self._rows(camera)] = value
+        self._push()
+        return self
+
+    def set_boxes(self, on: bool, camera=None) -> "AnnotateStyle":
+        """Draw the outlines of the first ``max_draw`` boxes, or not."""
+        return self._set(camera, "boxes", 1 if on else 0)
+
+    def set_labels(self, parts: str, camera=None) -> "AnnotateStyle":
+        """``"class"``, ``"id"``, ``"both"`` (``cls:id``) or ``"none"``."""
+        if parts not in ANNOTATE_LABELS:
+            raise ValueError(f"labels must be one of {tuple(ANNOTATE_LABELS)}, got {parts!r}")
+        return self._set(camera, "labels", ANNOTATE_LABELS[parts])
+
+    def set_colour_by(self, key: str, camera=None) -> "AnnotateStyle":
+        """Box colour from the ``"class"`` or from the ``"track"`` id (rows without an id fall
+        back to the class)."""
+        if key not in ANNOTATE_COLOUR_BY:
+            raise ValueError(f"colour_by must be 'class' or 'track', got {key!r}")
+        return self._set(camera, "colour_by", ANNOTATE_COLOUR_BY[key])
+
+    @staticmethod
+    def _int(name: str, v, lo: int, hi: int) -> int:
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        return int(v)
+
+    def set_thickness(self, t: int, camera=None) -> "AnnotateStyle":
+        """Outline thickness in thumbnail pixels, 1..4."""
+        return self._set(camera, "thickness", self._int("thickness", t, 1, 4))
+
+    def set_label_scale(self, s: int, camera=None) -> "AnnotateStyle":
+        """Glyph scale 1..2: cells of 6 x 8 or 12 x 16 pixels."""
+        return self._set(camera, "scale", self._int("label scale", s, 1, 2))
+
+    def set_privacy_block(self, block: int, camera=None) -> "AnnotateStyle":
+        """Mosaic block side in thumbnail pixels: 4, 8 or 16."""
+        if isinstance(block, bool) or block not in ANNOTATE_BLOCKS:
+            raise ValueError(f"privacy block must be one of {ANNOTATE_BLOCKS}, got {block!r}")
+        return self._set(camera, "block", int(block))
+
+    def set_max_draw(self, rows: int, camera=None) -> "AnnotateStyle":
+        """Only the first ``rows`` boxes get an outline or a label (privacy covers all)."""
+        return self._set(camera, "max_draw", self._int("max_draw", rows, 0, TRACK_MAX_DET))
+
+    def set_privacy_classes(self, classes, camera=None) -> "AnnotateStyle":
+        """Up to 8 class ids whose boxes are pixelated (an empty list: none)."""
+        classes = [self._int("privacy class", c, 0, 65535) for c in classes]
+        if len(classes) > ANNOTATE_MAX_CLASSES:
+            raise ValueError(f"at most {ANNOTATE_MAX_CLASSES} privacy classes, got "
+                             f"{len(classes)}")
+        row = torch.full((ANNOTATE_MAX_CLASSES,), -1, dtype=torch.int32)
+        row[:len(classes)] = torch.tensor(classes, dtype=torch.int32)
+        return self._set(camera, "privacy_classes", row)
+
+    def set_privacy_polygon(self, index: int, polygon, camera=None) -> "AnnotateStyle":
+        """Privacy polygon ``index`` (0..7): 3..8 pixel vertices, convex or not, in the frame
+        the boxes live in; every mosaic block with a pixel centre inside is pixelated."""
+        index = self._int("polygon index", index, 0, ANNOTATE_MAX_POLYGONS - 1)
+        polygon = list(polygon)
+        if not 3 <= len(polygon) <= ANNOTATE_MAX_VERTICES:
+            raise ValueError(f"a polygon has 3..{ANNOTATE_MAX_VERTICES} vertices, got "
+                             f"{len(polygon)}")
+        rows, h = self._rows(camera), self._views(self.host)
+        v = torch.zeros(ANNOTATE_MAX_VERTICES, 2, dtype=torch.int32)
+        v[:len(polygon)] = torch.tensor([_zone_q(p) for p in polygon], dtype=torch.int32)
+        h["vertex"][rows, index] = v
+        h["n_vertex"][rows, index] = len(polygon)
+        h["n_polygons"][rows] = h["n_polygons"][rows].clamp_min(index + 1)
+        self._push()
+        return self
+
+    def clear_privacy_polygons(self, camera=None) -> "AnnotateStyle":
+        rows, h = self._rows(camera), self._views(self.host)
+        h["vertex"][rows] = 0
+        h["n_vertex"][rows] = 0
+        h["n_polygons"][rows] = 0
+        self._push()
+        return self
+
+    def set_palette(self, colours, camera=None) -> "AnnotateStyle":
+        """Sixteen (R, G, B) colours; a box takes entry ``key & 15``."""
+        colours = [tuple(self._int("colour", c, 0, 255) for c in rgb) for rgb in colours]
+        if len(colours) != 16 or any(len(c) != 3 for c in colours):
+            raise ValueError("the palette has 16 (R, G, B) entries")
+        return self._set(camera, "palette", torch.tensor(
+            [r | g << 8 | b << 16 for r, g, b in colours], dtype=torch.int32))
+
+
+def annotate(images: torch.Tensor, style: AnnotateStyle, det: Optional[torch.Tensor] = None,
+             count: Optional[torch.Tensor] = None, track_id: Optional[torch.Tensor] = None,
+             src_hw=None, slot0: int = 0) -> torch.Tensor:
+    """Draw what the device knows into the thumbnails ``images`` uint8 [N, H, W, 3]
+    (contiguous, W % 4 == 0, H and W <= RESIZE_MAX_EXTENT), in place, and return them: the
+    outlines and ``cls:id`` labels of the boxes ``det`` fp32 [N, max_det, 6] / ``count`` int32
+    [N] / ``track_id`` int32 [N, max_det] (optional), and a mosaic over every box of a privacy
+    class and over the privacy polygons of ``style``.  ``src_hw`` = (Hs, Ws) <= 4096 is the pixel
+    frame the boxes and polygons live in (default: the thumbnail's own).  With ``det=None`` only
+    the polygons apply.  Row n is drawn in the style of camera ``slot0 + n``.  One launch on
+    the current stream, no host synchronisation, capturable (csrc/kernels/annotate.hip); GPU
+    and CPU (ops.reference.annotate, where the rules are written out) agree byte for byte."""
+    if not isinstance(style, AnnotateStyle):
+        raise TypeError(f"style must be an ops.AnnotateStyle, got {type(style).__name__}")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"images are uint8 [N, H, W, 3], got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    if not (1 <= h <= RESIZE_MAX_EXTENT and 1 <= w <= RESIZE_MAX_EXTENT) or w % 4:
+        raise ValueError(f"thumbnails of {h}x{w}: 1..{RESIZE_MAX_EXTENT}, width a multiple of 4")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    if images.device != style.device:
+        raise ValueError(f"images on {images.device}, style on {style.device}")
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > style.streams:
+        raise ValueError(f"cameras [{slot0}, {slot0 + n}) outside the style's {style.streams}")
+    hs, ws = (h, w) if src_hw is None else (int(src_hw[0]), int(src_hw[1]))
+    if not (1 <= hs <= ANNOTATE_MAX_SRC and 1 <= ws <= ANNOTATE_MAX_SRC):
+        raise ValueError(f"src_hw {hs}x{ws} outside 1..{ANNOTATE_MAX_SRC}")
+    if det is None:
+        if count is not None or track_id is not None:
+            raise ValueError("count and track_id come with det")
+    else:
+        if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6 or det.shape[0] != n:
+            raise ValueError(f"det must be fp32 [{n}, max_det, 6], got {det.dtype} "
+                             f"{tuple(det.shape)}")
+        max_det = int(det.shape[1])
+        if not 1 <= max_det <= TRACK_MAX_DET:
+            raise ValueError(f"annotate needs 1 <= max_det <= {TRACK_MAX_DET}, got {max_det}")
+        if count is None or count.dtype != torch.int32 or tuple(count.shape) != (n,):
+            raise ValueError(f"count must be int32 [{n}]")
+        if track_id is not None and (track_id.dtype != torch.int32
+                                     or tuple(track_id.shape) != (n, max_det)):
+            raise ValueError(f"track_id must be int32 [{n}, {max_det}], got {track_id.dtype} "
+                             f"{tuple(track_id.shape)}")
+        for name, t in (("det", det), ("count", count), ("track_id", track_id)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t is not None and t.device != images.device:
+                raise ValueError(f"images on {images.device}, {name} on {t.device}")
+    if images.is_cuda:
+        _native().annotate(images, style.table, style.font, det, count, track_id, hs, ws, slot0)
+    else:
+        _ref.annotate(images, style.host, style.font_host, det, count, track_id, (hs, ws), slot0)
+    return images
+
+
 def batchnorm_nhwc(x, scale, shift, relu=False, out=None):
     if out is None:
         out = torch.empty_like(x)

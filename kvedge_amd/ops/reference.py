@@ -925,3 +925,160 @@ def jpeg_encode(images, subsampling: str = "420", quality: int = 75, stats: bool
         files.append(bytes(out))
         counts.append(st)
     return (files, counts) if stats else files
+
+
+# ---------------------------------------------------------------------------
+# snapshot annotation: boxes, labels and privacy mosaic drawn into the thumbnails
+# ---------------------------------------------------------------------------
+# style table, int32 per camera (the layout csrc/kernels/annotate.hip reads)
+ANN_BOXES, ANN_LABELS, ANN_COLOUR_BY, ANN_THICKNESS, ANN_SCALE, ANN_BLOCK = 0, 1, 2, 3, 4, 5
+ANN_MAX_DRAW, ANN_N_POLY, ANN_PRIV_CLS, ANN_N_VERT, ANN_VERT, ANN_PALETTE = 6, 7, 8, 16, 24, 152
+ANN_TABLE_STRIDE = 168
+ANN_MAX = 8           # privacy classes, polygons and vertices per polygon, per camera
+ANN_MAX_DET = 300
+ANN_MAX_SRC = 4096    # the frame the boxes live in: quarter pixels stay inside 0..16384
+ANN_LABELS_MODES = ("none", "class", "id", "both")  # bit 0: class, bit 1: id
+ANN_GLYPHS = "0123456789:"
+# 5 x 7 glyphs, one row per word, bit 4 = the left column; the 8th row of a glyph is blank
+_ANN_FONT_ROWS = (
+    "01110 10001 10011 10101 11001 10001 01110",  # 0
+    "00100 01100 00100 00100 00100 00100 01110",  # 1
+    "01110 10001 00001 00010 00100 01000 11111",  # 2
+    "11111 00010 00100 00010 00001 10001 01110",  # 3
+    "00010 00110 01010 10010 11111 00010 00010",  # 4
+    "11111 10000 11110 00001 00001 10001 01110",  # 5
+    "00110 01000 10000 11110 10001 10001 01110",  # 6
+    "11111 00001 00010 00100 01000 01000 01000",  # 7
+    "01110 10001 10001 01110 10001 10001 01110",  # 8
+    "01110 10001 10001 01111 00001 00010 01100",  # 9
+    "00000 00100 00100 00000 00100 00100 00000",  # :
+)
+ANN_FONT_WORDS = 8 * len(ANN_GLYPHS)
+
+
+def annotate_font() -> np.ndarray:
+    """The font table int32 [88]: glyph g (``ANN_GLYPHS``) in words 8 g .. 8 g + 7."""
+    f = np.zeros(ANN_FONT_WORDS, np.int32)
+    for g, rows in enumerate(_ANN_FONT_ROWS):
+        for i, row in enumerate(rows.split()):
+            f[8 * g + i] = int(row, 2)
+    return f
+
+
+def annotate_block(v: int) -> int:
+    """The mosaic block a table word stands for: 16, 8 or 4 whatever it holds."""
+    return 16 if v >= 16 else 8 if v >= 8 else 4
+
+
+def annotate_rects(det, src_hw, hw):
+    """Quantised boxes fp32 [..., >= 4] in a (Hs, Ws) frame -> thumbnail rectangles int64
+    [..., 4] = (x0, y0, x1, y1), half open, never empty, covering every pixel of the (H, W)
+    thumbnail the box touches."""
+    (hs, ws), (h, w) = src_hw, hw
+    q = track_quantize(det[..., :4])
+    out = torch.empty_like(q)
+    for a, (src, dst) in enumerate(((ws, w), (hs, h))):
+        q1 = q[..., a].clamp_max(4 * src)
+        q2 = q[..., a + 2].clamp_max(4 * src)
+        lo = torch.clamp((q1 * dst) // (4 * src), max=dst - 1)
+        hi = (q2 * dst + 4 * src - 1) // (4 * src)
+        out[..., a] = lo
+        out[..., a + 2] = torch.minimum(torch.maximum(hi, lo + 1), torch.tensor(dst))
+    return out
+
+
+def annotate_text(labels: int, cls: int, tid: int) -> str:
+    """The label of a row: class digits, ':' when both parts show, digits of id % 100000; the
+    id part and the colon are dropped while id < 0 ('' = no label)."""
+    parts = []
+    if labels & 1:
+        parts.append(str(cls))
+    if labels & 2 and tid >= 0:
+        parts.append(str(tid % 100000))
+    return ":".join(parts)
+
+
+def annotate(images, table, font, det=None, count=None, track_id=None, src_hw=None, slot0=0):
+    """Draw into uint8 [N, H, W, 3] thumbnails, in place: THE definition the HIP kernel
+    (csrc/kernels/annotate.hip) equals byte for byte.  ``table`` int32 [S, 168] is the style
+    of every camera (row n of ``images`` uses row ``slot0 + n``), ``font`` int32 [88]; ``det``
+    fp32 [N, max_det, 6] / ``count`` int32 [N] / ``track_id`` int32 [N, max_det] or None are
+    the boxes in a ``src_hw`` = (Hs, Ws) pixel frame (default: the thumbnail's own).
+
+    Every output pixel is a function of the input picture and the tables.  From the top:
+    labels (lowest row index first), outlines (lowest row index first), the mosaic of the
+    privacy blocks, the picture.  Every count, size and index of the table is clamped as the
+    kernel clamps it."""
+    n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    hs, ws = (h, w) if src_hw is None else (int(src_hw[0]), int(src_hw[1]))
+    font = np.asarray(font).astype(np.int64)
+    ys, xs = torch.arange(h, dtype=torch.int64), torch.arange(w, dtype=torch.int64)
+    # pixel centres in quarter pixels of the source frame
+    cx = (((2 * xs + 1) * 2 * ws) // w)[None, :].expand(h, w)
+    cy = (((2 * ys + 1) * 2 * hs) // h)[:, None].expand(h, w)
+    for i in range(n):
+        tab = [int(v) for v in table[slot0 + i].tolist()]
+        img = images[i].numpy()
+        src = img.copy()
+        boxes, labels = tab[ANN_BOXES] != 0, tab[ANN_LABELS] & 3
+        by_track = tab[ANN_COLOUR_BY] == 1
+        t = min(max(tab[ANN_THICKNESS], 1), 4)
+        s = min(max(tab[ANN_SCALE], 1), 2)
+        blk = annotate_block(tab[ANN_BLOCK])
+        max_draw = min(max(tab[ANN_MAX_DRAW], 0), ANN_MAX_DET)
+        priv = [c for c in tab[ANN_PRIV_CLS:ANN_PRIV_CLS + ANN_MAX] if c >= 0]
+        cnt, rect, cls, tid = 0, None, None, None
+        if det is not None:
+            cnt = min(max(int(count[i]), 0), int(det.shape[1]))
+            rect = annotate_rects(det[i], (hs, ws), (h, w)).tolist()
+            cls = track_class(det[i, :, 5]).tolist()
+            tid = track_id[i].tolist() if track_id is not None else [-1] * int(det.shape[1])
+        # privacy: the pixels that are hidden, then whole blocks
+        hit = np.zeros((h, w), bool)
+        for r in range(cnt):
+            if cls[r] in priv:
+                x0, y0, x1, y1 = rect[r]
+                hit[y0:y1, x0:x1] = True
+        for z in range(min(max(tab[ANN_N_POLY], 0), ANN_MAX)):
+            nv = min(max(tab[ANN_N_VERT + z], 0), ANN_MAX)
+            if nv < 3:
+                continue
+            v = tab[ANN_VERT + 16 * z:ANN_VERT + 16 * z + 2 * nv]
+            hit |= point_in_polygon(cx, cy, list(zip(v[0::2], v[1::2]))).numpy()
+        for by in range(0, h, blk):
+            for bx in range(0, w, blk):
+                if hit[by:by + blk, bx:bx + blk].any():
+                    cell = src[by:by + blk, bx:bx + blk].astype(np.int64).reshape(-1, 3)
+                    img[by:by + blk, bx:bx + blk] = (cell.sum(0) + len(cell) // 2) // len(cell)
+        # outlines and labels, highest row first so that the lowest ends on top
+        drawn = range(min(cnt, max_draw) - 1, -1, -1)
+        colour = {}
+        for r in drawn:
+            key = tid[r] if by_track and tid[r] >= 0 else cls[r]
+            c = tab[ANN_PALETTE + (key & 15)]
+            colour[r] = (c & 255, (c >> 8) & 255, (c >> 16) & 255)
+        if boxes:
+            for r in drawn:
+                x0, y0, x1, y1 = rect[r]
+                ring = np.ones((y1 - y0, x1 - x0), bool)
+                ring[t:y1 - y0 - t, t:x1 - x0 - t] = False
+                img[y0:y1, x0:x1][ring] = colour[r]
+        for r in drawn:
+            text = annotate_text(labels, cls[r], tid[r])
+            if not text:
+                continue
+            x0, y0 = rect[r][0], rect[r][1]
+            lw, lh = s * (6 * len(text) + 1), 9 * s
+            cr, cg, cb = colour[r]
+            ink = 0 if (77 * cr + 150 * cg + 29 * cb) >> 8 >= 128 else 255
+            lab = np.empty((lh, lw, 3), np.uint8)
+            lab[:] = colour[r]
+            for k, ch in enumerate(text):
+                g = ANN_GLYPHS.index(ch)
+                for gy in range(7):
+                    for gx in range(5):
+                        if (font[8 * g + gy] >> (4 - gx)) & 1:
+                            yy, xx = s * (1 + gy), s * (1 + 6 * k + gx)
+                            lab[yy:yy + s, xx:xx + s] = ink
+            img[y0:y0 + lh, x0:x0 + lw] = lab[:h - y0, :w - x0]
+    return images
