@@ -36,13 +36,22 @@
 // holds v channels 4q .. 4q + 3, so cv2's second K step takes them as k = 8q .. 8q + 3 with
 // zeros in k = 8q + 4 .. 8q + 7, and the weights are read in that permuted order -- v never
 // goes through LDS.
-#include <stdlib.h>
-
 #include "common.h"
 #include "kvedge_kernels.h"
 
+// Timing switches of variant builds only (tools/c2f_probe.py); every bit makes the outputs
+// wrong: 1 identity activations, 2 no x loads, 4 no y stores.  (A bit 8, y staged through LDS
+// for whole-pixel stores, measured slower and was removed: profiles/r5_v10_c2f_probe.md.)
+//   KVEDGE_VARIANT=c2f1 KVEDGE_CFLAGS=-DKVEDGE_C2F_DIAG=1 python -m kvedge_amd._build
+#ifndef KVEDGE_C2F_DIAG
+#define KVEDGE_C2F_DIAG 0
+#endif
+static_assert((KVEDGE_C2F_DIAG & ~7) == 0, "KVEDGE_C2F_DIAG: bits 0..2 only");
+
 namespace kvedge {
 namespace {
+
+constexpr int kDiag = KVEDGE_C2F_DIAG;
 
 constexpr int kC2fRS = 6, kC2fRU = 4, kC2fRA = 6;  // two rows per iteration (below)
 typedef unsigned int c2f_u32x4 __attribute__((ext_vector_type(4)));
@@ -81,7 +90,7 @@ __device__ __forceinline__ bf16x4 c2f_pack4(floatx4 v) {
 }
 
 template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64, 3) void c2f16_kernel(const KvC2fParams p, int diag) {
+__global__ __launch_bounds__(WAVES * 64, 3) void c2f16_kernel(const KvC2fParams p) {
   constexpr int BPW = 1;  // one 16-pixel block per wave: W = 16 x WAVES
   extern __shared__ __attribute__((aligned(16))) char c2f_lds[];
   constexpr int W = 16 * WAVES;
@@ -138,10 +147,9 @@ __global__ __launch_bounds__(WAVES * 64, 3) void c2f16_kernel(const KvC2fParams 
     wm2f[j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwm2, off, 0, 0));
   }
 
-  // diag bit 1: identity instead of SiLU (timing only)
-  // bias-seeded accumulator -> SiLU (diag bit 1: identity, timing only) -> bf16
+  // bias-seeded accumulator -> SiLU (kDiag bit 0: identity, timing only) -> bf16
   auto c2f_act4 = [&](floatx4 acc) __attribute__((always_inline)) -> bf16x4 {
-    return c2f_pack4((diag & 1) ? acc : c2f_silu4f(acc));
+    return c2f_pack4((kDiag & 1) ? acc : c2f_silu4f(acc));
   };
 
   // 3x3 tap of lane quarter q in step j (the tenth tap re-reads tap 8: finite, weight 0)
@@ -157,7 +165,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void c2f16_kernel(const KvC2fParams 
   const __amdgpu_buffer_rsrc_t rx = c2f_rsrc(p.x, (long long)p.N * H * W * p.ldx * 2);
   const __amdgpu_buffer_rsrc_t ry = c2f_rsrc(p.y, (long long)p.N * H * W * p.ldy * 2);
   auto load_x = [&](int r, c2f_u32x4 (&dst)[BPW]) __attribute__((always_inline)) {
-    const bool ok = r >= 0 && r < H && r <= s1 + 3 && !(diag & 2);
+    const bool ok = r >= 0 && r < H && r <= s1 + 3 && !(kDiag & 2);
 #pragma unroll
     for (int b = 0; b < BPW; ++b) {
       const int px = (w + WAVES * b) * 16 + r16;
@@ -276,7 +284,7 @@ __global__ __launch_bounds__(WAVES * 64, 3) void c2f16_kernel(const KvC2fParams 
         const bf16x4 yv = c2f_act4(acc);
         __builtin_amdgcn_raw_buffer_store_b64(
             __builtin_bit_cast(c2f_u32x2, yv), ry,
-            (diag & 4) ? kC2fOOB : (unsigned)(ybase + nb * 16 + q * 4) * 2u, 0, 0);
+            (kDiag & 4) ? kC2fOOB : (unsigned)(ybase + nb * 16 + q * 4) * 2u, 0, 0);
       }
     }
   };
@@ -325,14 +333,6 @@ int c2f16_lds_bytes(int W) {
   return ((kC2fRS + kC2fRU) * (W + 2) + kC2fRA * W) * 16 * 2 + 96 * 4;  // + biases
 }
 
-// KVEDGE_C2F_DIAG (timing experiments, tools/c2f_probe.py): 1 identity activations, 2 no x
-// loads, 4 no y stores (bit 8, y staged through LDS for whole-pixel stores, measured slower:
-// profiles/r5_v10_c2f_probe.md, removed)
-int c2f_diag() {
-  const char* e = getenv("KVEDGE_C2F_DIAG");
-  return e ? atoi(e) : 0;
-}
-
 }  // namespace kvedge
 
 using namespace kvedge;
@@ -347,7 +347,6 @@ extern "C" int kv_c2f16_fused(const KvC2fParams* p, hipStream_t stream) {
       p->ldw2 < 48 || p->ldwm < 144)
     return -3;
   const int lds = c2f16_lds_bytes(p->W);
-  const int diag = c2f_diag();
   const unsigned grid = (unsigned)(p->N * (p->H / p->S));
   if (grid == 0) return 0;
   const void* fn = p->W == 160 ? reinterpret_cast<const void*>(&c2f16_kernel<10>)
@@ -355,8 +354,8 @@ extern "C" int kv_c2f16_fused(const KvC2fParams* p, hipStream_t stream) {
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
     return -7;
   if (p->W == 160)
-    hipLaunchKernelGGL(c2f16_kernel<10>, dim3(grid), dim3(10 * 64), (unsigned)lds, stream, *p, diag);
+    hipLaunchKernelGGL(c2f16_kernel<10>, dim3(grid), dim3(10 * 64), (unsigned)lds, stream, *p);
   else
-    hipLaunchKernelGGL(c2f16_kernel<5>, dim3(grid), dim3(5 * 64), (unsigned)lds, stream, *p, diag);
+    hipLaunchKernelGGL(c2f16_kernel<5>, dim3(grid), dim3(5 * 64), (unsigned)lds, stream, *p);
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }

@@ -79,6 +79,16 @@ struct DirectCfg {
 #endif
 constexpr int KPD = KV_DIRECT_PD;
 
+// Timing switches of variant builds only, on the direct-epilogue (DE) forms; every bit makes
+// the outputs wrong: bit 0 drops the stores, bit 1 the next-band patch prefetch, bit 2 the
+// MFMAs.
+//   KVEDGE_VARIANT=dd4 KVEDGE_CFLAGS=-DKVEDGE_DIRECT_DIAG=4 python -m kvedge_amd._build
+#ifndef KVEDGE_DIRECT_DIAG
+#define KVEDGE_DIRECT_DIAG 0
+#endif
+static_assert((KVEDGE_DIRECT_DIAG & ~7) == 0, "KVEDGE_DIRECT_DIAG: bits 0..2 only");
+constexpr int kDiag = KVEDGE_DIRECT_DIAG;
+
 // bytes of one patch buffer: the DMA form rounds up to whole 1-KB DMA instructions (the
 // last one may run past the patch) and keeps two buffers
 __host__ __device__ constexpr int direct_patch_alloc(int patch_bytes, bool dma) {
@@ -121,8 +131,7 @@ template <int CIN, int COUT, int S, int KK, int ACT, bool RES, bool U8 = false, 
 // file per lane, for weight blocks that do not fit 256 (CIN = 128: 288 weight VGPRs)
 __global__ __launch_bounds__(NT, (NT / 256) * OCC) void conv3x3_direct_kernel(const KvConvParams p, int kR,
                                                                 int PW, int patch_rows,
-                                                                FastDiv fPW, FastDiv fWo,
-                                                                int diag) {
+                                                                FastDiv fPW, FastDiv fWo) {
   static_assert(!U8 || (CIN == 16 && KK == 2 && S == 1), "frames-in form: the 2x2 s2d stem");
   static_assert(!PAIRS || U8, "paired raw-row loads: frames-in form only");
   // KK = 1: a 1x1 conv through the same band machinery (pad 0): YOLO's narrow C2f / Detect
@@ -394,8 +403,8 @@ __global__ __launch_bounds__(NT, (NT / 256) * OCC) void conv3x3_direct_kernel(co
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     } else if constexpr (DMA) {
-      // diag bit 1 (KVEDGE_DIRECT_DIAG, timing experiments only: wrong results): no prefetch
-      if (!(DE && (diag & 2))) dma_fetch(item + gridDim.x, patch + (cur ^ 1) * psz);
+      // kDiag bit 1 (variant builds, timing only: wrong results): no prefetch
+      if (!(DE && (kDiag & 2))) dma_fetch(item + gridDim.x, patch + (cur ^ 1) * psz);
     } else {
       fetch(item + gridDim.x);
     }
@@ -492,36 +501,23 @@ __global__ __launch_bounds__(NT, (NT / 256) * OCC) void conv3x3_direct_kernel(co
         if constexpr (kk + PD < C::KS) rd(IC<kk + PD>{});
         constexpr int younger = (C::KS - 1 - kk) < PD ? (C::KS - 1 - kk) : PD;
         lds_wait<younger>(af[kk % (PD + 1)]);
-        if (!(DE && (diag & 4)))  // diag bit 2: no MFMAs
+        if (!(DE && (kDiag & 4)))  // kDiag bit 2: no MFMAs
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wreg[kk], af[kk % (PD + 1)], acc, 0, 0, 0);
       });
       const int jr = b * 32 + fr;
       if constexpr (DE) {
         const int oy = oy0 + yl;
         const bool ok = jr < npix && oy < Ho;
-        if (diag & 1) continue;  // diag bit 0: no stores (the band-end wait then under-waits)
+        if (kDiag & 1) continue;  // kDiag bit 0: no stores (the band-end wait then under-waits)
         const int pix = (((n * Ho + oy) * Wo + xc) * p.ldy + p.y_coff + cb * 32) * 2;
         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        if (!RES && (diag & 8)) {
-          // diag bit 3: the first DE store form, 4 x 8 B per lane (lanes fr / fr + 32: channels
-          // [g*8, g*8+4) / [g*8+4, g*8+8)), 32 16-B segments per instruction
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            if (cb * 32 + g * 8 >= COUT) continue;
-            bf16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(act_c<ACT>(acc[4 * g + e]));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), ry,
-                                                  ok ? pix + (g * 8 + fh * 4) * 2 : kOOB, 0, 0);
-          }
-          continue;
-        }
         // Half-wave exchange, then 16 B per lane: for the group pair (2q, 2q+1) lane fr ends
         // with channels [16q, 16q+8) of pixel jr and lane fr + 32 with [16q+8, 16q+16).  One
-        // store instruction writes 32 pixels x 32 contiguous bytes (the 4 x 8-B form: 32 x 16 B).
-        // Same box, 2-5 % faster than the 8-B form; the stores still cost ~80 of 250 us on the
-        // Detect P3 stem slice (profiles/r4_v3_direct_diag.txt).
+        // store instruction writes 32 pixels x 32 contiguous bytes.  The first DE form (4 x 8-B
+        // stores per lane, 32 x 16 B per instruction) measured 2-5 % slower on the same box and
+        // is gone; the stores still cost ~80 of 250 us on the Detect P3 stem slice
+        // (profiles/r4_v3_direct_diag.txt).
         // Residual: the block's loads are this wave's youngest vector-memory ops -> vmcnt(0)
         // (older: the previous block's stores, issued a whole MFMA phase ago, and the patch DMA).
         if constexpr (RES) vm_wait<0>(rv[0], rv[1]);
@@ -581,7 +577,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * OCC) void conv3x3_direct_kernel(co
       // this wave's stores of the band (nbw blocks x ng groups) are its youngest vector-memory
       // ops: wait for everything older -- the next band's patch DMAs -- and leave them in flight
       const int nbw = ph < NPH ? (nblk - ph + NPH - 1) / NPH : 0;
-      const int ng = (!RES && (diag & 8)) ? min(4,(COUT - cb * 32 + 7) / 8) : min(2, (COUT - cb * 32 + 15) / 16);
+      const int ng = min(2, (COUT - cb * 32 + 15) / 16);
       direct_wait_vm_le(__builtin_amdgcn_readfirstlane(nbw * ng));
       cur ^= 1;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -697,7 +693,7 @@ __global__ __launch_bounds__(NT, (NT / 256) * OCC) void conv3x3_direct_kernel(co
   }
 }
 
-typedef void (*DirectFn)(const KvConvParams, int, int, int, FastDiv, FastDiv, int);
+typedef void (*DirectFn)(const KvConvParams, int, int, int, FastDiv, FastDiv);
 
 struct DirectEntry {
   int cin, cout, stride, kk, act;
@@ -922,14 +918,6 @@ static int direct_plan(const KvConvParams* p, int tile, int* kR, int* PW, int* r
   return idx;
 }
 
-// KVEDGE_DIRECT_DIAG (timing experiments on the direct-epilogue forms only; bits 0-2 make
-// the outputs wrong): bit 0 drops the stores, bit 1 the next-band patch prefetch, bit 2 the
-// MFMAs; bit 3 selects the first (4 x 8-B) store form, for same-box A/B.
-static int direct_diag() {
-  const char* e = getenv("KVEDGE_DIRECT_DIAG");
-  return e ? atoi(e) : 0;
-}
-
 static int direct_launch_one(const KvConvParams* p, int tile, hipStream_t stream) {
   int kR, PW, rows, lds;
   const int idx = direct_plan(p, tile, &kR, &PW, &rows, &lds);
@@ -946,7 +934,7 @@ static int direct_launch_one(const KvConvParams* p, int tile, hipStream_t stream
                           hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
     return -7;
   hipLaunchKernelGGL(fn, dim3(g), dim3(kDirect[idx].nt), (unsigned)lds, stream, *p, kR, PW, rows,
-                     make_fastdiv(PW), make_fastdiv(p->Wo), direct_diag());
+                     make_fastdiv(PW), make_fastdiv(p->Wo));
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

@@ -36,19 +36,14 @@
 //        reading wave's lgkmcnt(0) before a barrier the restaging wave passes first.
 // Steps past the last K-tile are staged out of range (zero fill, into halves already
 // consumed), so every phase issues the same two DMA ops and the counted waits stay exact.
-#include <stdlib.h>
-
 #include "conv_glds_kernel.inc"
 
-#ifndef KV_PP_DMA
-#define KV_PP_DMA 1
+// Ablation switch of variant builds only (outputs are wrong; see conv_pp_kernel's ABL):
+//   KVEDGE_VARIANT=ppabl22 KVEDGE_CFLAGS=-DKVEDGE_PP_ABL=22 python -m kvedge_amd._build
+#ifndef KVEDGE_PP_ABL
+#define KVEDGE_PP_ABL 0
 #endif
-#ifndef KV_PP_PRIO
-#define KV_PP_PRIO 1
-#endif
-#ifndef KV_PP_KEEPB
-#define KV_PP_KEEPB 1
-#endif
+static_assert((KVEDGE_PP_ABL & ~127) == 0, "KVEDGE_PP_ABL: bits 0..6 only");
 
 namespace kvedge {
 namespace {
@@ -65,12 +60,13 @@ namespace {
 // launch per tile.  The A and B staging descriptors switch tiles at the first A / B half
 // staged for the new tile (every later stage of the old tile precedes it).  Bias: two LDS
 // slots by tile parity (kLdsBias forms), the next tile's written at the end of an epilogue.
-// ABL (ablation instantiations, timing only -- outputs are wrong; KVEDGE_PP_ABL, tile 117,
-// MODE 0 and 1): bit 0 drops the MFMA clusters, bit 1 the fragment reads, bit 2 the LDS-DMA
-// staging, bit 3 the lgkmcnt(0) before each phase's first barrier, bit 4 both barriers of
-// every phase.  What is left of the phase period says what bounds it (tools/pp_abl.sh).
-// Bits 5 / 6: drop only the B (weight) / only the A (activation) staging DMAs.
-template <int BM, int BN, int MODE, bool PT, int ABL = 0>
+// ABL (ablation, timing only -- outputs are wrong; 0 unless the library is a variant built
+// with -DKVEDGE_PP_ABL=n): bit 0 drops the MFMA clusters, bit 1 the fragment reads, bit 2
+// the LDS-DMA staging, bit 3 the lgkmcnt(0) before each phase's first barrier, bit 4 both
+// barriers of every phase.  What is left of the phase period says what bounds it
+// (tools/pp_abl.py).  Bits 5 / 6: drop only the B (weight) / only the A (activation)
+// staging DMAs.
+template <int BM, int BN, int MODE, bool PT, int ABL = KVEDGE_PP_ABL>
 __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const KvConvParams p) {
   constexpr int kHA = BM / 2 * 64, kHB = BN / 2 * 64;  // bf16 elements per A / B half-tile
   constexpr int kStage = (BM + BN) * 64;               // one K-tile: A0 A1 B0 B1
@@ -246,9 +242,10 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const KvConvParams p) {
       for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int d = 0; d < 4; ++d) acc[a][b][c][d] = floatx4{0.f, 0.f, 0.f, 0.f};
-  // B fragments per N half (KV_PP_KEEPB: B0's stay in registers from phase 0 to phase 3, so
-  // the K-step reads 24 fragments instead of 28 -- the ablation puts the cost of the staging
-  // in its contention with these LDS reads, profiles/r6_v10_pp_ablation_pmc.md)
+  // B fragments per N half: B0's stay in registers from phase 0 to phase 3, so the K-step
+  // reads 24 fragments instead of 28 -- the ablation puts the cost of the staging in its
+  // contention with these LDS reads (profiles/r6_v10_pp_ablation_pmc.md,
+  // profiles/r6_v17_pp_keepb_ab.md)
   bf16x8 afr[2][4], bfrq[2][2][2];  // [ks][block] / [qn][ks][block]
   auto read_a = [&](const bf16* st, int qm) __attribute__((always_inline)) {
     const bf16* As = st + half_off(qm);
@@ -267,13 +264,8 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const KvConvParams p) {
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int row = wn * 32 + b * 16 + fr;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(Bs + row * 64 + (((ks * 4 + fh) ^ sw(row)) << 3));
-        if (KV_PP_KEEPB && qn == 1) bfrq[1][ks][b] = v;
-        else bfrq[0][ks][b] = v;
+        bfrq[qn][ks][b] = *reinterpret_cast<const bf16x8*>(Bs + row * 64 + (((ks * 4 + fh) ^ sw(row)) << 3));
       }
-  };
-  auto bfr_of = [&](int qn, int ks, int b) __attribute__((always_inline)) -> const bf16x8& {
-    return (KV_PP_KEEPB && qn == 1) ? bfrq[1][ks][b] : bfrq[0][ks][b];
   };
   auto mma = [&](int qm, int qn) __attribute__((always_inline)) {
 #pragma unroll
@@ -283,45 +275,24 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const KvConvParams p) {
 #pragma unroll
         for (int tm = 0; tm < 4; ++tm)
           acc[qn][tn][qm][tm] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr_of(qn, ks, tn), afr[ks][tm], acc[qn][tn][qm][tm], 0, 0, 0);
+              __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfrq[qn][ks][tn], afr[ks][tm], acc[qn][tn][qm][tm], 0, 0, 0);
   };
-  // one phase: reads + staging (+ the per-tile counted wait), barrier, MFMAs, barrier.
-  // KV_PP_DMA (A/B knob): 1 = the two DMA ops after the fragment reads (default), 0 = before
-  // them, 2 = inside the MFMA cluster (after 8 of its 16 MFMAs: the read section is then
-  // reads only; the tile-end wait counts one phase less in flight)
-  auto mma_half = [&](int qm, int qn, int ks) __attribute__((always_inline)) {
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int tm = 0; tm < 4; ++tm)
-        acc[qn][tn][qm][tm] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr_of(qn, ks, tn), afr[ks][tm], acc[qn][tn][qm][tm], 0, 0, 0);
-  };
+  // one phase: reads, then the staging DMA ops (+ the per-tile counted wait), barrier, MFMAs
+  // at raised priority, barrier
   auto phase = [&](const bf16* st, int qm, int qn, auto RA, auto RB, int sh, int sT, bool tile_end)
       __attribute__((always_inline)) {
-    if (KV_PP_DMA == 0) stage(sh, sT);
     if constexpr (decltype(RA)::value && (ABL & 2) == 0) read_a(st, qm);
     if constexpr (decltype(RB)::value && (ABL & 2) == 0) read_b(st, qn);
-    if (KV_PP_DMA == 1) stage(sh, sT);
-    // tile kt+1 landed (this wave's part): 3 half-tiles stay in flight (2 when this phase's
-    // DMA is issued later, inside its MFMA cluster)
-    if (tile_end) wait_vm<KV_PP_DMA == 2 ? AO + BO : 2 * AO + BO>();
+    stage(sh, sT);
+    // tile kt+1 landed (this wave's part): 3 half-tiles stay in flight
+    if (tile_end) wait_vm<2 * AO + BO>();
     if constexpr ((ABL & 8) == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if constexpr ((ABL & 16) == 0) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (KV_PP_PRIO) __builtin_amdgcn_s_setprio(1);
-    if constexpr ((ABL & 1) != 0) {
-    } else if (KV_PP_DMA == 2) {
-      mma_half(qm, qn, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      stage(sh, sT);
-      __builtin_amdgcn_sched_barrier(0);
-      mma_half(qm, qn, 1);
-    } else {
-      mma(qm, qn);
-    }
-    if (KV_PP_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(1);
+    if constexpr ((ABL & 1) == 0) mma(qm, qn);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr ((ABL & 16) == 0) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -423,9 +394,8 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const KvConvParams p) {
     phase(st, 0, 0, T1{}, T1{}, 2, T + 1, false);  // B0 of K-step T+1
     phase(st, 0, 1, T0{}, T1{}, 0, T + 2, false);  // A0 of K-step T+2
     phase(st, 1, 1, T1{}, T0{}, 3, T + 2, false);  // B1 of K-step T+2
-    // (KV_PP_KEEPB: B0 is still in registers from phase 0, no reads in this phase)
-    if constexpr (KV_PP_KEEPB) phase(st, 1, 0, T0{}, T0{}, 1, T + 2, true);
-    else phase(st, 1, 0, T0{}, T1{}, 1, T + 2, true);   // A1 of K-step T+2; wait: K-step T+1
+    // A1 of K-step T+2; wait: K-step T+1 (B0 is still in registers from phase 0: no reads)
+    phase(st, 1, 0, T0{}, T0{}, 1, T + 2, true);
     if (PT && ++c_kt == nk) {  // the tile's last K-step: epilogue, fresh accumulators
       epilogue(c_i);
       c_kt = 0;
@@ -490,25 +460,6 @@ int pp_launch(const KvConvParams* p, int tile, hipStream_t stream) {
   ConvKernelFn fn = wide ? (pt ? KV_PP_FN(256, 256, true) : KV_PP_FN(256, 256, false))
                          : (pt ? KV_PP_FN(512, 128, true) : KV_PP_FN(512, 128, false));
 #undef KV_PP_FN
-  static const int abl = getenv("KVEDGE_PP_ABL") ? atoi(getenv("KVEDGE_PP_ABL")) : 0;
-  if (abl && wide && !pt && (mode == 0 || mode == 1)) {
-#define KV_PP_ABL(a) (mode == 0 ? conv_pp_kernel<256, 256, 0, false, a> : conv_pp_kernel<256, 256, 1, false, a>)
-    switch (abl) {
-      case 1: fn = KV_PP_ABL(1); break;
-      case 2: fn = KV_PP_ABL(2); break;
-      case 4: fn = KV_PP_ABL(4); break;
-      case 6: fn = KV_PP_ABL(6); break;
-      case 8: fn = KV_PP_ABL(8); break;
-      case 16: fn = KV_PP_ABL(16); break;
-      case 22: fn = KV_PP_ABL(22); break;
-      case 32: fn = KV_PP_ABL(32); break;
-      case 64: fn = KV_PP_ABL(64); break;
-      case 34: fn = KV_PP_ABL(34); break;
-      case 66: fn = KV_PP_ABL(66); break;
-      default: return -6;
-    }
-#undef KV_PP_ABL
-  }
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(512), 0, stream, *p);
   return hipGetLastError() == hipSuccess ? 0 : -7;
 }

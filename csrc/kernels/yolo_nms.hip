@@ -1,4 +1,3 @@
-#include <stdlib.h>
 // K9 YOLOv8 decode and K10 class-aware NMS for gfx950.  SURVEY.md §2.5, §7.3(2).
 //
 // Decode: one workgroup per 64 consecutive anchors of one (image, level): the
@@ -22,8 +21,19 @@
 #include "common.h"
 #include "kvedge_kernels.h"
 
+// Timing switches of nms_kernel, variant builds only (tools/nms_probe.py); every bit makes the
+// outputs wrong: bit 0 skips the greedy suppression, bit 1 the top-set sort, bit 2 writes the
+// per-phase durations over each image's first output row.
+//   KVEDGE_VARIANT=nms2 KVEDGE_CFLAGS=-DKVEDGE_NMS_DIAG=2 python -m kvedge_amd._build
+#ifndef KVEDGE_NMS_DIAG
+#define KVEDGE_NMS_DIAG 0
+#endif
+static_assert((KVEDGE_NMS_DIAG & ~7) == 0, "KVEDGE_NMS_DIAG: bits 0..2 only");
+
 namespace kvedge {
 namespace {
+
+constexpr int kDiag = KVEDGE_NMS_DIAG;
 
 constexpr int kRegMax = 16;
 constexpr float kMaxWH = 7680.f;  // class offset for class-aware NMS
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
                                                   const int* __restrict__ cls, int A,
                                                   float conf, float iou_thr, int max_det,
                                                   float* __restrict__ out,
-                                                  int* __restrict__ count, int diag) {
+                                                  int* __restrict__ count) {
   __shared__ __attribute__((aligned(16))) unsigned long long keys[kMaxCand];
   __shared__ __attribute__((aligned(16))) float kept[4 * 320];
   __shared__ int kept_c[320];
@@ -166,7 +176,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
   __shared__ int s_n2, s_T, s_nsel;
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
-  const unsigned long long t_start = (diag & 4) ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const unsigned long long t_start = (kDiag & 4) ? __builtin_amdgcn_s_memrealtime() : 0ull;
   const float* sc = scores + (long long)n * A;
   // wave-aggregated compaction: one LDS atomic per wave and pass (popcount of the ballot)
   // instead of one per candidate -- with random-init heads nearly all 8400 anchors pass
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
   };
   compact();
   const int cnt = min(ncand, kMaxCand);
-  // diag bit 2: per-phase wall-clock stamps (s_memrealtime, 100 MHz) -> the image's output rows
+  // kDiag bit 2: per-phase wall-clock stamps (s_memrealtime, 100 MHz) -> the image's output rows
   unsigned long long t_ph[4] = {t_start, 0, 0, 0};
   // bitonic sort of K[0, n) (padded with zero keys to a power of two), descending
   auto bitonic = [&](unsigned long long* K, int n) __attribute__((always_inline)) {
@@ -259,7 +269,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
   };
   unsigned long long* K = keys;
   int nsel = cnt;
-  bool sorted = false;  // the top set already came out of its sort (bucket or fallback)
+  bool sorted = false;     // K is a top set that went through its own sort below
   bool clobbered = false;  // keys[] now holds the sorted top set, not all candidates
   int rest_T = -1;         // threshold bin of the top set (the rest = keys below it)
   if (cnt > kSel) {
@@ -293,82 +303,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
       }
     }
     __syncthreads();
-    // Bucket sort of the top set (the 2048-key bitonic network was 43 of
-    // the ~100 us a crowded image spends in NMS, profiles/r4_v5_nms_probe.txt).  The
-    // histogram already orders the keys by bin; each top-set bin gets a descending slot range
-    // (suffix sums of its counts), keys are scattered into their bin's range with one LDS
-    // atomic each, and only keys that share a bin are ranked against each other.  The bin
-    // cursors live in the free tail of keys[] (cnt <= kMaxCand - kBins / 2 -- the top set
-    // of a 640x640 image has at most 8400 candidates); a bin with more than kBinRankMax keys
-    // (a degenerate score pile-up) falls back to the bitonic network.
-    constexpr int kBinRankMax = 64;
-    int* cur = reinterpret_cast<int*>(keys + (kMaxCand - kBins / 2));
-    // measured level-to-slower than the bitonic network on the bench's decode output (101.3
-    // vs 96.7 us per b256 slice, profiles/r5_v5_nms_probe_bucket.txt: the kernel is set by
-    // its slowest image, whose compaction and suppression dominate), so opt-in (diag bit 3)
-    const bool bucket = s_nsel <= kSelMax && cnt <= kMaxCand - kBins / 2 && (diag & 8);
-    if (bucket) {
-      const int T = s_T;
-      if (tid < 64) {  // wave 0: lane L owns bins [32 L, 32 L + 32); descending exclusive sums
-        int sum = 0, mx = 0;
-        for (int b = 0; b < 32; ++b) {
-          const int bb = tid * 32 + b;
-          const int c = bb >= T ? hist[bb] : 0;
-          sum += c;
-          mx = max(mx, c);
-        }
-        int suf = sum;  // inclusive suffix over lanes >= L
-        for (int off = 1; off < 64; off <<= 1) {
-          const int v = __shfl_down(suf, off);
-          if (tid + off < 64) suf += v;
-        }
-        int run = suf - sum;  // slots taken by the bins above this lane's
-        for (int b = 31; b >= 0; --b) {
-          const int bb = tid * 32 + b;
-          cur[bb] = run;  // start of bin bb (the scatter advances it to the bin's end)
-          run += bb >= T ? hist[bb] : 0;
-        }
-        for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
-        if (tid == 0) s_n2 = mx;
-      }
-      __syncthreads();
-      const int binmax = s_n2;
-      __syncthreads();  // every thread has read s_n2 before the fallback below reuses it
-      if (binmax <= kBinRankMax) {
-        for (int i = tid; i < cnt; i += blockDim.x) {
-          const unsigned long long key = keys[i];
-          const int b = bin_of(key);
-          if (b >= T) sel[atomicAdd(&cur[b], 1)] = key;
-        }
-        __syncthreads();
-        // rank inside the bin: cur[b] is now the bin's end, its start the end of bin b + 1
-        const int ns = s_nsel;
-        unsigned long long mine[kSelMax / (64 * kNmsWaves)];
-        int dst[kSelMax / (64 * kNmsWaves)];
-#pragma unroll
-        for (int k = 0; k < kSelMax / (64 * kNmsWaves); ++k) {
-          const int i = tid + k * 64 * kNmsWaves;
-          dst[k] = -1;
-          if (i < ns) {
-            const unsigned long long key = sel[i];
-            const int b = bin_of(key);
-            const int lo0 = b + 1 < kBins ? cur[b + 1] : 0, hi0 = cur[b];
-            int r = 0;
-            for (int j = lo0; j < hi0; ++j) r += sel[j] > key;
-            mine[k] = key;
-            dst[k] = lo0 + r;
-          }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kSelMax / (64 * kNmsWaves); ++k)
-          if (dst[k] >= 0) sel[dst[k]] = mine[k];
-        __syncthreads();
-        K = sel;
-        nsel = ns;
-      }
-    }
-    if (s_nsel <= kSelMax && K == keys) {
+    if (s_nsel <= kSelMax) {
       const int T = s_T;
       rest_T = T;
       const int ln = tid & 63;
@@ -387,7 +322,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
       __syncthreads();
       K = sel;
       nsel = s_n2;
-      if (!(diag & 2)) {
+      if (!(kDiag & 2)) {
         if (nsel <= kRankSortMax) {
           // one rank pass into keys[0, nsel) instead of the bitonic network's log^2
           // barrier-separated stages (a 1382-candidate image: ~28 us of bitonic, r5 probe);
@@ -402,22 +337,22 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
       sorted = true;
     }
   }
-  if (diag & 4) t_ph[1] = __builtin_amdgcn_s_memrealtime();
+  if (kDiag & 4) t_ph[1] = __builtin_amdgcn_s_memrealtime();
   // Small sets (random-init heads: ~100 candidates per image) are sorted by rank: each thread
   // counts the keys above its own with broadcast LDS reads and writes its key to that slot --
   // one pass and one barrier instead of the bitonic network's log^2 barrier-separated stages
   // (28 at 128 keys, 42 us per image measured: profiles/r4_v5_nms_probe.txt).  Keys are unique
   // (the index is in the low word), so the ranks are a permutation.
-  if (K == sel && cnt > kSel) sorted = true;  // the bucket sort above
-  if (!(diag & 2) && !sorted) {
-    if (K == keys && nsel <= kRankSortMax) {
+  // (kDiag bit 1: no sort, timing only)
+  if (!(kDiag & 2) && !sorted) {  // K == keys: every candidate
+    if (nsel <= kRankSortMax) {
       rank_sort(keys, sel, nsel);
       K = sel;
     } else {
-      bitonic(K, nsel);  // diag bit 1: no top-set sort (timing only)
+      bitonic(K, nsel);
     }
   }
-  if (diag & 4) t_ph[2] = __builtin_amdgcn_s_memrealtime();
+  if (kDiag & 4) t_ph[2] = __builtin_amdgcn_s_memrealtime();
   float* o = out + (long long)n * max_det * 6;
   const int lane = tid & 63, wv = tid >> 6;
   const float* bx = boxes + (long long)n * A * 4;
@@ -526,7 +461,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
       nk = s_nk;
     }
   };
-  if (!(diag & 1)) greedy(K, 0, nsel);  // diag bit 0: no suppression (timing only)
+  if (!(kDiag & 1)) greedy(K, 0, nsel);  // kDiag bit 0: no suppression (timing only)
   else nk = max_det;
   if (nk < max_det && nsel < cnt) {
     // the top set ran out: sort everything (its first nsel keys are the top set again,
@@ -535,7 +470,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
     // same set: compaction order does not matter, the sort fixes it)
     if (clobbered) compact();
     const int nrest = cnt - nsel;
-    if (rest_T >= 0 && nrest <= kRankSortMax && !(diag & 2)) {
+    if (rest_T >= 0 && nrest <= kRankSortMax && !(kDiag & 2)) {
       // only the keys BELOW the top set still need an order: compact them (bin < T) into
       // sel, rank-sort them into keys[0, nrest) and continue the greedy there -- they all
       // rank below every top-set key, so this is the full sort's tail (the crowded image's
@@ -563,7 +498,7 @@ __global__ __launch_bounds__(64 * kNmsWaves) void nms_kernel(const float* __rest
   }
   for (int i = nk * 6 + tid; i < max_det * 6; i += blockDim.x) o[i] = 0.f;
   if (tid == 0) count[n] = nk;
-  if (diag & 4) {
+  if (kDiag & 4) {
     t_ph[3] = __builtin_amdgcn_s_memrealtime();
     __syncthreads();
     if (tid == 0) {  // phase durations in 10-ns ticks: compaction+select, sort, suppression
@@ -602,12 +537,7 @@ extern "C" int kv_nms(const float* boxes, const float* scores, const int* cls, i
                       hipStream_t s) {
   if (max_det > 300 || max_det <= 0 || A > kMaxCand) return -1;
   if (N <= 0) return 0;
-  // KVEDGE_NMS_DIAG (timing experiments only; outputs wrong): bit 0 skips the greedy
-  // suppression, bit 1 the top-set sort; bit 2 writes per-phase durations into each image's
-  // first output row; bit 3 (outputs right) sorts the top set with the histogram bucket sort
-  // instead of the bitonic network (A/B)
-  const char* dg = getenv("KVEDGE_NMS_DIAG");
   hipLaunchKernelGGL(nms_kernel, dim3(N), dim3(64 * kNmsWaves), 0, s, boxes, scores, cls, A, conf_thres,
-                     iou_thres, max_det, out, count, dg ? atoi(dg) : 0);
+                     iou_thres, max_det, out, count);
   return hipGetLastError() == hipSuccess ? 0 : -100;
 }

@@ -444,40 +444,61 @@ def test_nms_dense_overlaps():
     assert (o.cpu() - o_ref).abs().max() < 1e-4
 
 
-@pytest.mark.parametrize("bucket", [False, True])
-@pytest.mark.parametrize("case", ["spread", "clustered", "ties", "piles"])
-def test_nms_top_set(case, bucket, monkeypatch):
-    """YOLO-sized candidate lists (8400 anchors, most above conf) through the NMS top-set
-    path: 'spread' reaches max_det inside the bucket-sorted top set; 'clustered' (one class,
+@pytest.mark.parametrize("case", ["spread", "clustered", "ties", "piles", "rest"])
+def test_nms_top_set(case):
+    """YOLO-sized candidate lists (8400 anchors) through the NMS top-set path: 'spread' (most
+    anchors above conf) reaches max_det inside the sorted top set; 'clustered' (one class,
     boxes piled on few centres) exhausts the top set first and falls back to the full sort;
     'ties' (scores on 8 levels) puts > 2048 keys in one histogram bin (full-sort path);
-    'piles' (scores on 96 levels) keeps the top set under 2048 keys but puts > 64 in a bin
-    (the bucket sort's bitonic fallback).  bucket: the opt-in histogram bucket sort of the
-    top set (KVEDGE_NMS_DIAG bit 3) instead of the default bitonic network."""
-    if bucket:
-        monkeypatch.setenv("KVEDGE_NMS_DIAG", "8")
-    g = torch.Generator().manual_seed(5)
-    A, N = 8400, 3
-    if case == "clustered":
-        ctr = torch.rand(N, 4, 2, generator=g)[:, torch.randint(0, 4, (A,), generator=g)] * 600
+    'piles' (scores on 96 levels) keeps the top set under 2048 keys with > 64 in a bin;
+    'rest' (1500 candidates: 1300 piled on 4 centres, the 200 lowest-scoring isolated) has a
+    top set small enough to be rank-sorted over keys[], which runs out before max_det: the
+    candidates are compacted again and the keys below the top set (<= 1024) are rank-sorted
+    alone to continue the greedy pass."""
+    if case == "rest":
+        g = torch.Generator().manual_seed(7)
+        A, N, ncand, niso = 8400, 2, 1500, 200
+        ctr = (torch.rand(N, 4, 2, generator=g) * 500 + 50)[:, torch.randint(0, 4, (A,), generator=g)]
         wh = torch.rand(N, A, 2, generator=g) * 4 + 60
+        boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], -1)
         cls = torch.zeros(N, A, dtype=torch.int32)
+        scores = torch.full((N, A), 0.05)
+        cell = torch.arange(niso)
+        xy = torch.stack([cell % 20, cell // 20], -1).float() * 30 + 20  # 20 x 10 grid, 30 px pitch
+        for i in range(N):
+            idx = torch.randperm(A, generator=g)[:ncand]
+            sc = torch.rand(ncand, generator=g) * 0.7 + 0.3
+            scores[i, idx] = sc
+            iso = idx[sc.argsort()[:niso]]  # the lowest-scoring candidates: 10 x 10, far apart
+            boxes[i, iso] = torch.cat([xy, xy + 10], -1)
     else:
-        ctr = torch.rand(N, A, 2, generator=g) * 640
-        wh = torch.rand(N, A, 2, generator=g) * 40 + 4
-        cls = torch.randint(0, 80, (N, A), generator=g, dtype=torch.int32)
-    boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], -1)
-    scores = torch.rand(N, A, generator=g) * 0.7 + 0.3
-    if case == "ties":
-        scores = (scores * 8).floor() / 8 + 0.05
-    if case == "piles":
-        scores = (scores * 96).floor() / 96 + 0.002
+        g = torch.Generator().manual_seed(5)
+        A, N = 8400, 3
+        if case == "clustered":
+            ctr = torch.rand(N, 4, 2, generator=g)[:, torch.randint(0, 4, (A,), generator=g)] * 600
+            wh = torch.rand(N, A, 2, generator=g) * 4 + 60
+            cls = torch.zeros(N, A, dtype=torch.int32)
+        else:
+            ctr = torch.rand(N, A, 2, generator=g) * 640
+            wh = torch.rand(N, A, 2, generator=g) * 40 + 4
+            cls = torch.randint(0, 80, (N, A), generator=g, dtype=torch.int32)
+        boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], -1)
+        scores = torch.rand(N, A, generator=g) * 0.7 + 0.3
+        if case == "ties":
+            scores = (scores * 8).floor() / 8 + 0.05
+        if case == "piles":
+            scores = (scores * 96).floor() / 96 + 0.002
     o_ref, n_ref = ops.nms(boxes, scores, cls, conf=0.25, iou=0.7, max_det=300)
     o, n = ops.nms(boxes.cuda(), scores.cuda(), cls.cuda(), conf=0.25, iou=0.7, max_det=300)
     assert torch.equal(n.cpu(), n_ref), (n, n_ref)
     assert (o.cpu() - o_ref).abs().max() < 1e-4
-    if case == "clustered":
+    if case in ("clustered", "rest"):
         assert int(n_ref.max()) < 300  # the top set alone never reaches max_det here
+    if case == "rest":
+        # ... and it does run out: the 768 best scores alone keep fewer boxes than all of them
+        top = torch.zeros_like(scores).scatter_(1, scores.topk(768, dim=1).indices, 1.0)
+        _, n_top = ops.nms(boxes, scores * top, cls, conf=0.25, iou=0.7, max_det=300)
+        assert bool((n_top < n_ref).all()), (n_top, n_ref)
 
 
 @pytest.mark.parametrize("tile", [-1] + list(range(6, DIRECT0)) + sorted(NLOOP_DUAL) + [NLOOP0 + 8]

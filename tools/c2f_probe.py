@@ -3,6 +3,15 @@
 (x read + y written once) and the four-launch block it replaces, per strip height S.
 
   python tools/c2f_probe.py --batch 256 --strips 40,20,8
+
+Every number is of the library this process loaded (printed next to it).  The kernel's timing
+switches are compile-time (-DKVEDGE_C2F_DIAG=n: 1 identity activations, 2 no x loads, 4 no y
+stores; outputs wrong), so each value is a variant build timed in a fresh process:
+
+  for d in 1 2 4; do
+    KVEDGE_VARIANT=c2f$d KVEDGE_CFLAGS=-DKVEDGE_C2F_DIAG=$d python -m kvedge_amd._build
+    KVEDGE_LIB=_C_c2f$d.so python tools/c2f_probe.py --batch 256 --strips 40
+  done
 """
 import argparse
 import os
@@ -17,8 +26,6 @@ def main():
     ap.add_argument("--hw", type=int, default=160)
     ap.add_argument("--strips", default="40,20,8")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--diags", default="", help="KVEDGE_C2F_DIAG values to time at the first S "
-                    "(1 identity act, 2 no x loads, 4 no y stores, 8 y via LDS staging)")
     a = ap.parse_args()
     import torch
     from kvedge_amd import ops
@@ -49,24 +56,19 @@ def main():
         torch.cuda.synchronize()
         return st.elapsed_time(en) / (3 * a.iters) * 1e3
 
+    lib = ops.library_path()
     print(f"c2f16 b{a.batch} @{a.hw}: compulsory {byts / 1e6:.0f} MB")
     for S in [int(s) for s in a.strips.split(",")]:
         us = timeit(lambda: ops.c2f16(x, blk.cv1.w, blk.cv1.b, b1.w, b1.b, b2.w, b2.b,
                                       blk.cv2.w, blk.cv2.b, out=y, S=S))
-        print(f"  fused S={S}: {us:.1f} us  {byts / us / 1e3:.0f} GB/s", flush=True)
-    S0 = int(a.strips.split(",")[0])
-    for d in [int(v) for v in a.diags.split(",") if v]:
-        os.environ["KVEDGE_C2F_DIAG"] = str(d)
-        us = timeit(lambda: ops.c2f16(x, blk.cv1.w, blk.cv1.b, b1.w, b1.b, b2.w, b2.b,
-                                      blk.cv2.w, blk.cv2.b, out=y, S=S0))
-        print(f"  fused S={S0} diag={d}: {us:.1f} us", flush=True)
-    os.environ.pop("KVEDGE_C2F_DIAG", None)
+        print(f"  fused S={S}: {us:.1f} us  {byts / us / 1e3:.0f} GB/s  [{lib}]", flush=True)
     ops.C2F_ENABLED = False
     us = timeit(lambda: blk(x, out=y))
-    print(f"  four launches: {us:.1f} us", flush=True)
+    print(f"  four launches: {us:.1f} us  [{lib}]", flush=True)
     z = torch.empty_like(x)
     us = timeit(lambda: z.copy_(x))
-    print(f"  torch copy of x (same bytes): {us:.1f} us  {byts / us / 1e3:.0f} GB/s", flush=True)
+    print(f"  torch copy of x (same bytes): {us:.1f} us  {byts / us / 1e3:.0f} GB/s  [torch]",
+          flush=True)
 
 
 if __name__ == "__main__":

@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
-"""Phase-budget ablation of the v14 kernel (conv_pp.hip, tile 117): times one layer with
-parts of the 8-phase loop compiled out (KVEDGE_PP_ABL: 1 no MFMA clusters, 2 no fragment
-reads, 4 no LDS-DMA staging, 8 no lgkmcnt(0) before the first barrier, 16 no barriers, and
-sums of those).  Timing only -- the ablated outputs are wrong.
+"""Phase-budget ablation of the v14 kernel (conv_pp.hip, tile 117): times one layer in the
+library this process loaded.  The ablations are compile-time (-DKVEDGE_PP_ABL=n: 1 no MFMA
+clusters, 2 no fragment reads, 4 no LDS-DMA staging, 8 no lgkmcnt(0) before the first
+barrier, 16 no barriers, 32 / 64 no B / no A staging, and sums of those), so each value is a
+variant build of its own, timed in a fresh process.  Timing only -- an ablated library's
+outputs are wrong; the default library has none of it.
 
-  for a in 0 1 2 4 6 8 16 22; do KVEDGE_PP_ABL=$a python tools/pp_abl.py --layer s3.c2; done
+  python tools/pp_abl.py --layer s3.c2
+  for a in 1 2 4 6 8 16 22; do
+    KVEDGE_VARIANT=ppabl$a KVEDGE_CFLAGS=-DKVEDGE_PP_ABL=$a python -m kvedge_amd._build
+    KVEDGE_LIB=_C_ppabl$a.so python tools/pp_abl.py --layer s3.c2
+  done
 """
 import argparse
 import os
@@ -56,7 +62,7 @@ def main():
         torch.cuda.synchronize()
         ts.append(st.elapsed_time(en) / 10 * 1e3)
     ts.sort()
-    print(f"{a.layer} b{a.batch} tile {a.tile} abl {os.environ.get('KVEDGE_PP_ABL', '0')}: "
+    print(f"{a.layer} b{a.batch} tile {a.tile} [{ops.library_path()}]: "
           f"{ts[len(ts) // 2]:.1f} us per launch (median of 5 x 10)")
 
 
