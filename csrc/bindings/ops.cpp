@@ -1083,6 +1083,60 @@ void annotate(at::Tensor& images, const at::Tensor& table, const at::Tensor& fon
   TORCH_CHECK(rc == 0, "kvedge: annotate failed rc=", rc);
 }
 
+// K23: motion regions (csrc/kernels/motion_blobs.hip).  mask uint8 [N,GH,GW]; params int32
+// [S,4]; ignore uint8 [S,GH,GW]; camera n of mask is stream slot0 + n.  Everything is validated
+// before the launch: a rejected call leaves det, count and labels untouched.
+void motion_blobs(const at::Tensor& mask, const at::Tensor& params, const at::Tensor& ignore,
+                  at::Tensor& det, at::Tensor& count, at::Tensor& labels, int64_t slot0,
+                  int64_t cell, int64_t Hs, int64_t Ws, int64_t connectivity) {
+  check_dev(mask, "mask");
+  check_dev(params, "params");
+  check_dev(ignore, "ignore");
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(labels, "labels");
+  TORCH_CHECK(Hs >= 1 && Hs <= 4096 && Ws >= 1 && Ws <= 4096,
+              "kvedge: motion_blobs frame size 1..4096, got ", Hs, "x", Ws);
+  TORCH_CHECK(cell == 8 || cell == 16 || cell == 32, "kvedge: motion_blobs cell is 8, 16 or 32");
+  TORCH_CHECK(connectivity == 4 || connectivity == 8,
+              "kvedge: motion_blobs connectivity is 4 or 8, got ", connectivity);
+  const int64_t GH = (Hs + cell - 1) / cell, GW = (Ws + cell - 1) / cell;
+  TORCH_CHECK(GH * GW <= kv_motion_blobs_max_cells(), "kvedge: motion_blobs grid ", GH, "x", GW,
+              " exceeds ", kv_motion_blobs_max_cells(), " cells");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.dim() == 3 && mask.size(1) == GH &&
+                  mask.size(2) == GW, "kvedge: motion_blobs mask uint8 [N,GH,GW]");
+  const int64_t N = mask.size(0);
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
+              "kvedge: motion_blobs params int32 [S,4]");
+  const int64_t S = params.size(0);
+  TORCH_CHECK(ignore.scalar_type() == at::kByte && ignore.dim() == 3 && ignore.size(0) == S &&
+                  ignore.size(1) == GH && ignore.size(2) == GW,
+              "kvedge: motion_blobs ignore uint8 [S,GH,GW]");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == N &&
+                  det.size(2) == 6, "kvedge: motion_blobs det fp32 [N,max_blobs,6]");
+  const int64_t R = det.size(1);
+  TORCH_CHECK(R >= 1 && R <= 64, "kvedge: motion_blobs max_blobs is 1..64, got ", R);
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == N,
+              "kvedge: motion_blobs count int32 [N]");
+  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.dim() == 3 && labels.size(0) == N &&
+                  labels.size(1) == GH && labels.size(2) == GW,
+              "kvedge: motion_blobs labels int32 [N,GH,GW]");
+  TORCH_CHECK(S < (1ll << 24) && N <= 65535, "kvedge: motion_blobs too many streams");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: motion_blobs streams [", slot0, ", ",
+              slot0 + N, ") outside the regions' ", S);
+  TORCH_CHECK(mask.device() == params.device() && mask.device() == ignore.device() &&
+                  mask.device() == det.device() && mask.device() == count.device() &&
+                  mask.device() == labels.device(),
+              "kvedge: motion_blobs operands on different devices");
+  const c10::DeviceGuard g(mask.device());
+  const int rc = kv_motion_blobs(mask.data_ptr<uint8_t>(), params.data_ptr<int>(),
+                                 ignore.data_ptr<uint8_t>(), det.data_ptr<float>(),
+                                 count.data_ptr<int>(), labels.data_ptr<int>(), (int)N, (int)S,
+                                 (int)slot0, (int)Hs, (int)Ws, (int)cell, (int)R,
+                                 (int)connectivity, cur_stream(mask));
+  TORCH_CHECK(rc == 0, "kvedge: motion_blobs failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -1214,6 +1268,8 @@ TORCH_LIBRARY(kvedge, m) {
         "-> ()");
   m.def("annotate(Tensor(a!) images, Tensor table, Tensor font, Tensor? det, Tensor? count, "
         "Tensor? track_id, int Hs, int Ws, int slot0) -> ()");
+  m.def("motion_blobs(Tensor mask, Tensor params, Tensor ignore, Tensor(a!) det, Tensor(b!) count, "
+        "Tensor(c!) labels, int slot0, int cell, int Hs, int Ws, int connectivity) -> ()");
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1263,6 +1319,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("frame_watch", frame_watch);
   m.impl("jpeg_encode", jpeg_encode);
   m.impl("annotate", annotate);
+  m.impl("motion_blobs", motion_blobs);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

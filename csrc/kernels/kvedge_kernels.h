@@ -266,6 +266,22 @@ int kv_annotate_font_words(void);
 int kv_annotate(unsigned char* images, const int* table, const int* font, const float* det,
                 const int* count, const int* track_id, int N, int S, int slot0, int H, int W,
                 int Hs, int Ws, int max_det, hipStream_t s);
+// K23 (motion_blobs.hip): motion regions of streams [slot0, slot0 + N), one launch, one
+// workgroup per camera.  mask uint8 [N,GH,GW] (bit 0 = moved: K20's motion_mask), ignore uint8
+// [S,GH,GW] (non-zero = masked out) and params int32 [S,4] = min_cells, cls, 0, 0 (clamped into
+// 1..C and 0..65535) are only read; GH = ceil(Hs / cell), GW = ceil(Ws / cell), C = GH GW <=
+// kv_motion_blobs_max_cells() = 32768.  The active cells are grouped under 4- or
+// 8-connectivity; the max_blobs largest components of at least min_cells cells (ties: the lower
+// first cell) go to det fp32 [N,max_blobs,6] = pixel box, cells, cls; count int32 [N]; labels
+// int32 [N,GH,GW] = the cell's row in det, or -1.  Every element written; bit-identical to
+// ops.reference.motion_blobs; the rule and the LDS layout are at the top of motion_blobs.hip.
+// Returns -1 Hs or Ws outside 1..4096, -2 slot0 + N > S, -3 cell not 8/16/32, -4 more than
+// 32768 cells, -5 max_blobs outside 1..64, -6 connectivity not 4/8, -7 misaligned operand,
+// -9 N too large; nothing is written then.  N == 0 launches nothing.
+int kv_motion_blobs_max_cells(void);
+int kv_motion_blobs(const unsigned char* mask, const int* params, const unsigned char* ignore,
+                    float* det, int* count, int* labels, int N, int S, int slot0, int Hs, int Ws,
+                    int cell, int max_blobs, int connectivity, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

@@ -23,12 +23,17 @@ class KvWatched:
     """inner outputs ``(...)`` -> ``(..., cam_stats, motion_mask)``.  ``frame_hw``: the size of
     the frames the engine serves from (InferenceEngine ``frame_hw``); None = model-size frames.
     ``params``: thresholds by name (ops.WATCH_PARAMS), for every camera; ``watch_state``
-    (``set_params``) changes them between steps without recapturing."""
+    (``set_params``) changes them between steps without recapturing.  ``regions``: an
+    ops.MotionRegions of the same streams and grid; the outputs then become
+    ``(..., blob_det, blob_count, cam_stats, motion_mask)`` -- the ``max_blobs`` largest
+    connected blobs of moving cells per camera as detection rows (ops.motion_blobs), at
+    ``blob_index``."""
 
     stateful = True  # InferenceEngine passes slot0 = first batch row of the slice
 
     def __init__(self, inner, streams: int, frame_hw=None, cell: int = 16, row_step: int = 1,
-                 bg_shift: int = 4, **params):
+                 bg_shift: int = 4, regions=None, max_blobs: int = 16, connectivity: int = 8,
+                 **params):
         self.inner = inner
         self.device = inner.device
         self.image_size = getattr(inner, "image_size", 224)
@@ -40,6 +45,23 @@ class KvWatched:
         self._other = {}  # states for frames of another size (the autotuner's model-size run)
         self.watch_resets = 0  # bumped by reset(): host-side totals start over
         self._inner_stateful = bool(getattr(inner, "stateful", False))
+        # motion regions (ops.motion_blobs on the mask, same step): blob_det / blob_count go in
+        # front of the watch's two outputs, at ``blob_index`` (None: off)
+        self.regions, self.blob_index = regions, None
+        self.max_blobs, self.connectivity = int(max_blobs), int(connectivity)
+        self._other_regions = {}
+        if regions is not None:
+            if not isinstance(regions, ops.MotionRegions):
+                raise TypeError("regions must be an ops.MotionRegions, got "
+                                f"{type(regions).__name__}")
+            if (regions.streams, regions.grid) != (self.streams, self.watch_state.grid):
+                raise ValueError(f"regions cover {regions.streams} streams on a grid of "
+                                 f"{regions.grid}, the watch {self.streams} on "
+                                 f"{self.watch_state.grid}")
+            if not 1 <= self.max_blobs <= ops.BLOB_MAX_BLOBS:
+                raise ValueError(f"max_blobs {max_blobs} outside 1..{ops.BLOB_MAX_BLOBS}")
+            if self.connectivity not in ops.BLOB_CONNECTIVITY:
+                raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
 
     def _new_state(self, hw) -> "ops.WatchState":
         st = ops.WatchState(self.streams, hw, self.cell, self.row_step, self.bg_shift,
@@ -82,12 +104,26 @@ class KvWatched:
             self._other[hw] = self._new_state(hw)
         return self._other[hw]
 
+    def _regions_for(self, hw) -> "ops.MotionRegions":
+        if hw == self.regions.frame_hw:
+            return self.regions
+        if hw not in self._other_regions:  # (default rules: the run only sizes the tiles)
+            self._other_regions[hw] = ops.MotionRegions(self.streams, hw, self.cell,
+                                                        device=self.device)
+        return self._other_regions[hw]
+
     def _watch(self, out, src: torch.Tensor, slot0: int, src_format: str = "rgb"):
         hw = ((int(src.shape[1]) * 2 // 3, int(src.shape[2])) if src_format == "nv12"
               else (int(src.shape[1]), int(src.shape[2])))
         stats, mask = ops.frame_watch(src, self._state_for(hw), slot0=slot0,
                                       src_format=src_format)
-        return (*out, stats, mask)
+        if self.regions is None:
+            return (*out, stats, mask)
+        det, cnt, _ = ops.motion_blobs(mask, self._regions_for(hw), slot0=slot0,
+                                       max_blobs=self.max_blobs,
+                                       connectivity=self.connectivity)
+        self.blob_index = len(out)
+        return (*out, det, cnt, stats, mask)
 
     def __call__(self, frames_u8: torch.Tensor, slot0: int = 0):
         """Model-size frames: watched as RGB."""

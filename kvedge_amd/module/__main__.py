@@ -125,6 +125,18 @@ def main(argv=None):
                     help="mean neighbour difference below which the picture is `flat`")
     ap.add_argument("--watch-hold", type=int, default=d.watch_hold,
                     help="frames a condition must hold before its alarm (1..255)")
+    ap.add_argument("--watch-regions", action="store_true",
+                    help="--watch: group the moving cells into connected blobs on the device "
+                         "and report the largest per camera as boxes (`regions`)")
+    ap.add_argument("--watch-region-max", type=int, default=d.watch_region_max,
+                    help="regions reported per camera, 1..64")
+    ap.add_argument("--watch-region-connectivity", type=int,
+                    default=d.watch_region_connectivity, choices=[4, 8])
+    ap.add_argument("--watch-region-min-cells", type=int, default=d.watch_region_min_cells,
+                    help="blobs of fewer cells are dropped (live: no rebuild)")
+    ap.add_argument("--watch-ignore-json", default="",
+                    help="cells that never count as moving: '[{\"name\": \"tree\", \"polygon\": "
+                         "[[x, y], ...], \"cameras\"?}]' in frame pixels (live: no rebuild)")
     ap.add_argument("--snapshots", action="store_true",
                     help="encode every camera's frame as a JPEG thumbnail on the device; "
                          "pictures leave on output `snapshots` with watch alarms and "
@@ -196,6 +208,10 @@ def main(argv=None):
                        watch_scene_share=a.watch_scene_share,
                        watch_dark_level=a.watch_dark_level,
                        watch_flat_level=a.watch_flat_level, watch_hold=a.watch_hold,
+                       watch_regions=a.watch_regions, watch_region_max=a.watch_region_max,
+                       watch_region_connectivity=a.watch_region_connectivity,
+                       watch_region_min_cells=a.watch_region_min_cells,
+                       watch_ignore=a.watch_ignore_json,
                        snapshots=a.snapshots, snapshot_width=a.snapshot_width,
                        snapshot_subsampling=a.snapshot_subsampling,
                        snapshot_quality=a.snapshot_quality,

@@ -52,6 +52,7 @@ import os
 import random
 import time
 from dataclasses import replace
+from functools import partial
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -461,9 +462,17 @@ class ModuleApp:
 
             # outermost: it looks at the frames, whatever the inner model makes of them
             size = cfg.resolved_image_size()
+            regions = None
+            if cfg.watch_regions:  # the motion grid labelled into boxes, same step
+                from .watch import build_motion_regions
+
+                regions = build_motion_regions(cfg, dev)
             self.model = KvWatched(self.model, cfg.batch, frame_hw=cfg.frame_hw() or (size, size),
                                    cell=cfg.watch_cell, row_step=cfg.watch_row_step,
-                                   bg_shift=cfg.watch_bg_shift, **cfg.watch_params())
+                                   bg_shift=cfg.watch_bg_shift, regions=regions,
+                                   max_blobs=cfg.watch_region_max,
+                                   connectivity=cfg.watch_region_connectivity,
+                                   **cfg.watch_params())
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -599,10 +608,14 @@ class ModuleApp:
         if self.snapshots is not None and nsteps > 0 and self.engine.outputs is not None:
             # the pictures of the last step: lengths to the host, bytes only for what is sent
             totals = self.camera_totals.update() if self.camera_totals is not None else None
+            from .watch import camera_regions
+
+            regions = (partial(camera_regions, self.model, self.engine.outputs)
+                       if getattr(self.model, "blob_index", None) is not None else None)
             self.snapshots.step(self.engine.outputs, totals, self.clock(),
                                 self.state["total_steps"], self.cfg.snapshot_every_s,
                                 self.cfg.snapshot_max_bytes,
-                                lambda m: self.tr.send_message("snapshots", m))
+                                lambda m: self.tr.send_message("snapshots", m), regions)
         if not self._first_inference_stamped and nsteps > 0:
             self._first_inference_stamped = True
             self._stamp("module_first_inference")
@@ -809,8 +822,13 @@ class ModuleApp:
             return {}
         from .watch import alarm_counts
 
-        return {"cameras": alarm_counts(out[-2]),
-                "camera_alarms": self.camera_totals.update().summed()}
+        res = {"cameras": alarm_counts(out[-2]),
+               "camera_alarms": self.camera_totals.update().summed()}
+        if getattr(self.model, "blob_index", None) is not None:
+            from .watch import regions_summary
+
+            res["regions"] = regions_summary(self.model, out)
+        return res
 
     # ---------------------------------------------------------------- handlers
     # Handlers run on the module thread from transport.poll(); they only queue work
@@ -836,6 +854,14 @@ class ModuleApp:
                 and self.cfg.watch_params() != old.watch_params()):
             # thresholds live in device memory: the captured step reads them every replay
             self.model.watch_state.set_params(None, **self.cfg.watch_params())
+        if (getattr(self.model, "regions", None) is not None
+                and not self.cfg.needs_rebuild(old)
+                and any(getattr(self.cfg, k) != getattr(old, k)
+                        for k in ModuleConfig.REGION_LIVE_KEYS)):
+            # so do min_cells and the ignore cells of the motion regions
+            from .watch import apply_motion_regions
+
+            apply_motion_regions(self.model.regions, self.cfg)
         if (self.snapshots is not None and not self.cfg.needs_rebuild(old)
                 and self.cfg.snapshot_quality != old.snapshot_quality):
             # the quantisation tables live in device memory, like the watch thresholds
@@ -910,7 +936,21 @@ class ModuleApp:
                 if self.camera_totals is None or self.engine.outputs is None:
                     return 400, {"error": "watch is off"}
                 self.camera_totals.update()
-                return 200, {"cameras": self.camera_totals.per_camera(self.engine.outputs[-2]),
+                cams = self.camera_totals.per_camera(self.engine.outputs[-2])
+                if getattr(self.model, "blob_index", None) is not None:
+                    from .watch import REGIONS_PER_MESSAGE, camera_regions
+
+                    for d, rows in zip(cams, camera_regions(self.model, self.engine.outputs)):
+                        d["regions"] = rows[:REGIONS_PER_MESSAGE]
+                        d["regions_total"] = len(rows)
+                return 200, {"cameras": cams, "rank": self.rank}
+            if name == "regions":  # every camera's motion regions of the last step, in full
+                if (getattr(self.model, "blob_index", None) is None
+                        or self.engine.outputs is None):
+                    return 400, {"error": "watch_regions is off"}
+                from .watch import camera_regions
+
+                return 200, {"cameras": camera_regions(self.model, self.engine.outputs),
                              "rank": self.rank}
             if name == "snapshot":  # {camera: n}: that camera's picture of the last step
                 if self.snapshots is None or self.engine is None:

@@ -19,6 +19,7 @@ ZONE_ANCHORS = ("bottom", "centre")
 MAX_REGIONS = 8  # lines, and zones, per camera (csrc/kernels/zones.hip)
 SNAPSHOT_SUBSAMPLINGS = ("420", "444")
 SNAPSHOT_LABELS = ("none", "class", "id", "both")
+MAX_REGION_CELLS = 32768  # cells ops.motion_blobs labels (csrc/kernels/motion_blobs.hip)
 MAX_PRIVACY = 8  # privacy classes, and privacy zones, per camera (csrc/kernels/annotate.hip)
 
 
@@ -77,6 +78,18 @@ def _privacy_zones(v) -> Tuple[Dict[str, Any], ...]:
                 raise ValueError(f"snapshot_privacy_zones[{i}]: unknown keys ['class']")
     return tuple({k: r[k] for k in ("name", "cameras", "polygon")}
                  for r in _regions(v, "snapshot_privacy_zones"))
+
+
+def _ignore_zones(v) -> Tuple[Dict[str, Any], ...]:
+    """The ``watch_ignore`` twin key: polygons per camera, shaped like the privacy zones."""
+    if isinstance(v, str):
+        v = json.loads(v) if v.strip() else []
+    if isinstance(v, (list, tuple)):
+        for i, r in enumerate(v):
+            if isinstance(r, dict) and "class" in r:
+                raise ValueError(f"watch_ignore[{i}]: unknown keys ['class']")
+    return tuple({k: r[k] for k in ("name", "cameras", "polygon")}
+                 for r in _regions(v, "watch_ignore"))
 
 
 def _int_tuple(v, what: str) -> Tuple[int, ...]:
@@ -164,6 +177,16 @@ class ModuleConfig:
     watch_dark_level: float = 24.0
     watch_flat_level: float = 1.5
     watch_hold: int = 8
+    # motion regions (ops.motion_blobs): the moving cells grouped into connected blobs
+    # (watch_region_connectivity 4 / 8), the watch_region_max (1..64) largest of at least
+    # watch_region_min_cells cells reported per camera as boxes; the cells under the
+    # watch_ignore polygons ([{name, polygon: [[x, y], ...], cameras?}], frame pixels) never
+    # count.  min_cells and the polygons are read on the device at every step
+    watch_regions: bool = False
+    watch_region_max: int = 16
+    watch_region_connectivity: int = 8
+    watch_region_min_cells: int = 1
+    watch_ignore: Tuple[Dict[str, Any], ...] = ()
     # camera snapshots (ops.jpeg_encode): every step each camera's current frame is resized on
     # the device to snapshot_width pixels wide (the height follows the frame's shape) and
     # encoded as a baseline JPEG of snapshot_subsampling ("420" / "444") at snapshot_quality.
@@ -215,7 +238,8 @@ class ModuleConfig:
                "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
                "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
-               "watch_bg_shift", "snapshots", "snapshot_width", "snapshot_subsampling",
+               "watch_bg_shift", "watch_regions", "watch_region_max",
+               "watch_region_connectivity", "snapshots", "snapshot_width", "snapshot_subsampling",
                "snapshot_annotate")
 
     def __post_init__(self):
@@ -223,6 +247,7 @@ class ModuleConfig:
             object.__setattr__(self, kind, _regions(getattr(self, kind), kind))
         object.__setattr__(self, "snapshot_privacy_zones",
                            _privacy_zones(self.snapshot_privacy_zones))
+        object.__setattr__(self, "watch_ignore", _ignore_zones(self.watch_ignore))
         object.__setattr__(self, "snapshot_privacy_classes",
                            _int_tuple(self.snapshot_privacy_classes, "snapshot_privacy_classes"))
 
@@ -312,6 +337,32 @@ class ModuleConfig:
             raise ValueError("watch_hold must be 1..255")
         if self.watch and self.model == "simulated-temperature":
             raise ValueError("watch needs frames: a vision model")
+        # the motion regions' ranges (ops.MotionRegions, csrc/kernels/motion_blobs.hip)
+        if not 1 <= self.watch_region_max <= 64:
+            raise ValueError("watch_region_max must be 1..64")
+        if self.watch_region_connectivity not in (4, 8):
+            raise ValueError("watch_region_connectivity must be 4 or 8")
+        if not 1 <= self.watch_region_min_cells <= MAX_REGION_CELLS:
+            raise ValueError(f"watch_region_min_cells must be 1..{MAX_REGION_CELLS}")
+        for r in self.watch_ignore:
+            if r["cameras"] is not None and not all(0 <= c < self.batch for c in r["cameras"]):
+                raise ValueError(f"watch_ignore {r['name']!r}: cameras must be 0..batch - 1")
+            if len(r["polygon"]) < 3:
+                raise ValueError(f"watch_ignore {r['name']!r} needs 3 or more vertices")
+        base = ModuleConfig.__dataclass_fields__
+        if not self.watch_regions:
+            for k in self.REGION_KEYS[1:]:
+                if getattr(self, k) != base[k].default:
+                    raise ValueError(f"{k} needs watch_regions true")
+        else:
+            if not self.watch:
+                raise ValueError("watch_regions label the watch's motion grid: they need watch "
+                                 "true")
+            h, w = self.frame_hw() or (self.resolved_image_size(),) * 2
+            cells = -(-h // self.watch_cell) * -(-w // self.watch_cell)
+            if cells > MAX_REGION_CELLS:
+                raise ValueError(f"watch_regions label at most {MAX_REGION_CELLS} cells; "
+                                 f"{h}x{w} at watch_cell {self.watch_cell} has {cells}")
         if not 16 <= self.snapshot_width <= 1920:
             raise ValueError("snapshot_width must be 16..1920")
         if self.snapshot_subsampling not in SNAPSHOT_SUBSAMPLINGS:
@@ -389,6 +440,8 @@ class ModuleConfig:
                 v = _privacy_zones(v)
             elif k == "snapshot_privacy_classes":
                 v = _int_tuple(v, k)
+            elif k == "watch_ignore":
+                v = _ignore_zones(v)
             elif isinstance(cur, tuple):
                 v = _regions(v, k)
             else:
@@ -421,6 +474,10 @@ class ModuleConfig:
     WATCH_KEYS = ("watch", "watch_cell", "watch_row_step", "watch_bg_shift",
                   "watch_motion_level", "watch_motion_share", "watch_scene_share",
                   "watch_dark_level", "watch_flat_level", "watch_hold")
+
+    REGION_KEYS = ("watch_regions", "watch_region_max", "watch_region_connectivity",
+                   "watch_region_min_cells", "watch_ignore")
+    REGION_LIVE_KEYS = ("watch_region_min_cells", "watch_ignore")
 
     SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
                      "snapshot_every_s", "snapshot_max_bytes")
@@ -464,6 +521,12 @@ class ModuleConfig:
         if all(getattr(self, k) == getattr(base, k) for k in self.WATCH_KEYS):
             for k in self.WATCH_KEYS:
                 d.pop(k)
+        # and the motion-region keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.REGION_KEYS):
+            for k in self.REGION_KEYS:
+                d.pop(k)
+        else:
+            d["watch_ignore"] = list(d["watch_ignore"])
         # and the snapshot keys
         if all(getattr(self, k) == getattr(base, k) for k in self.SNAPSHOT_KEYS):
             for k in self.SNAPSHOT_KEYS:

@@ -78,9 +78,12 @@ class SnapshotSender:
         return out
 
     def step(self, outputs, totals, now: float, step: int, every_s: float, max_bytes: int,
-             send) -> None:
-        """After a step: send what is due through ``send(message)``."""
+             send, regions=None) -> None:
+        """After a step: send what is due through ``send(message)``.  ``regions``: a callable
+        returning the step's motion regions per camera (module.watch.camera_regions); an
+        ``alarm:motion`` message then carries its camera's."""
         lengths = outputs[self.stage.snap_index + 1].to("cpu").tolist()  # syncs with the device
+        rows = None  # the step's regions, fetched once when the first message needs them
         for cam, reason in self.due(totals, now, every_s):
             n = int(lengths[cam])
             if n < 0 or n > max_bytes:  # (negative: it did not even fit the device row)
@@ -91,6 +94,9 @@ class SnapshotSender:
                    "height": msg["height"], "bytes": n, "jpeg_b64": msg["jpeg_b64"]}
             if "annotated" in msg:
                 out["annotated"] = True
+            if regions is not None and reason == "alarm:motion":
+                rows = regions() if rows is None else rows
+                out["regions"] = rows[cam]
             send(out)
             self.sent += 1
 

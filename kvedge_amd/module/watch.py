@@ -4,6 +4,8 @@ from __future__ import annotations
 
 from typing import Any, Dict, List
 
+import torch
+
 from .. import ops
 from ..models.watching import decode_stats
 
@@ -61,3 +63,41 @@ def alarm_counts(stats) -> Dict[str, int]:
     """``{condition: cameras whose alarm bit is set now}`` from ``cam_stats`` [N, 16]."""
     alarms = stats[:, 5].to("cpu")
     return {name: int(((alarms >> c) & 1).sum()) for c, name in enumerate(ops.WATCH_CONDITIONS)}
+
+
+# -- motion regions (ops.motion_blobs behind KvWatched(regions=...))
+REGIONS_PER_MESSAGE = 8  # per camera in a telemetry message; `regions_total` has the count
+
+
+def apply_motion_regions(regions, cfg) -> "ops.MotionRegions":
+    """min_cells and the ignore polygons of the config into an ops.MotionRegions: both are read
+    on the device at every step, so this needs no rebuild."""
+    regions.set_min_cells(min(cfg.watch_region_min_cells, regions.grid[0] * regions.grid[1]))
+    polys: List[list] = [[] for _ in range(regions.streams)]
+    for r in cfg.watch_ignore:
+        for cam in (r["cameras"] if r["cameras"] is not None else range(regions.streams)):
+            polys[cam].append(r["polygon"])
+    # every camera's cells on the host, then one upload
+    return regions.set_ignore(None, torch.stack([regions.rasterise(p) for p in polys]))
+
+
+def build_motion_regions(cfg, device) -> "ops.MotionRegions":
+    size = cfg.resolved_image_size()
+    return apply_motion_regions(
+        ops.MotionRegions(cfg.batch, cfg.frame_hw() or (size, size), cfg.watch_cell,
+                          device=device), cfg)
+
+
+def camera_regions(model, outputs) -> List[List[List[int]]]:
+    """Per camera the reported blobs of the step as [x1, y1, x2, y2, cells], largest first."""
+    det = outputs[model.blob_index].to("cpu")  # syncs with the device
+    cnt = outputs[model.blob_index + 1].to("cpu").tolist()
+    return [[[int(v) for v in row[:5]] for row in det[cam, :n].tolist()]
+            for cam, n in enumerate(cnt)]
+
+
+def regions_summary(model, outputs) -> List[Dict[str, Any]]:
+    """The telemetry's ``regions``: one entry per camera with at least one region --
+    ``camera``, at most REGIONS_PER_MESSAGE ``regions`` and ``regions_total``."""
+    return [{"camera": cam, "regions": rows[:REGIONS_PER_MESSAGE], "regions_total": len(rows)}
+            for cam, rows in enumerate(camera_regions(model, outputs)) if rows]

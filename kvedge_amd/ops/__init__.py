@@ -1419,6 +1419,168 @@ def frame_watch(src: torch.Tensor, state: WatchState, slot0: int = 0, src_format
 
 
 # ---------------------------------------------------------------------------
+# motion regions: the watch's motion grid -> connected blobs as detection rows
+# ---------------------------------------------------------------------------
+BLOB_MAX_CELLS = _ref.BLOB_MAX_CELLS
+BLOB_MAX_BLOBS = _ref.BLOB_MAX_BLOBS
+BLOB_CLASS = _ref.BLOB_CLASS
+BLOB_CONNECTIVITY = (4, 8)
+
+
+def check_blob_grid(frame_hw, cell: int) -> Tuple[int, int]:
+    """The (GH, GW) grid of ``frame_hw`` at ``cell``, refused above ``BLOB_MAX_CELLS`` cells."""
+    hs, ws = int(frame_hw[0]), int(frame_hw[1])
+    if not (1 <= hs <= WATCH_MAX_EXTENT and 1 <= ws <= WATCH_MAX_EXTENT):
+        raise ValueError(f"motion regions need frames of 1..{WATCH_MAX_EXTENT}, got {hs}x{ws}")
+    if cell not in WATCH_CELLS:
+        raise ValueError(f"cell must be one of {WATCH_CELLS}, got {cell}")
+    grid = (-(-hs // cell), -(-ws // cell))
+    if grid[0] * grid[1] > BLOB_MAX_CELLS:
+        raise ValueError(f"motion regions label at most {BLOB_MAX_CELLS} cells; {hs}x{ws} at "
+                         f"cell {cell} is {grid[0]}x{grid[1]} = {grid[0] * grid[1]}")
+    return grid
+
+
+class MotionRegions:
+    """What ops.motion_blobs reads per camera, for ``streams`` cameras of ``frame_hw`` = (Hs, Ws)
+    pixels on a ``cell``-pixel grid: ``params`` int32 [S, 4] = min_cells, cls, 0, 0 and
+    ``ignore`` uint8 [S, GH, GW] (non-zero: the cell never counts as moving) on ``device``, with
+    host mirrors.  ``camera=None`` in a setter means every camera.  The kernel reads both at run
+    time and clamps min_cells into 1..GH GW and cls into 0..65535: a setter takes effect from
+    the next call, or the next replay of a captured step."""
+
+    def __init__(self, streams: int, frame_hw, cell: int = 16, device="cpu"):
+        if isinstance(streams, bool) or int(streams) < 1:
+            raise ValueError(f"streams must be >= 1, got {streams!r}")
+        self.grid = check_blob_grid(frame_hw, cell)
+        self.streams, self.cell = int(streams), int(cell)
+        self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        cpu = torch.device(device).type == "cpu"
+        self._params = torch.zeros(self.streams, 4, dtype=torch.int32)
+        self._ignore = torch.zeros(self.streams, *self.grid, dtype=torch.uint8)
+        self._params[:, 0], self._params[:, 1] = 1, BLOB_CLASS
+        self.params = self._params if cpu else self._params.to(device)
+        self.ignore = self._ignore if cpu else self._ignore.to(device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.params.device
+
+    def _rows(self, camera):
+        if camera is None:
+            return slice(None)
+        if isinstance(camera, bool) or not 0 <= int(camera) < self.streams:
+            raise ValueError(f"camera {camera} outside 0..{self.streams - 1}")
+        return slice(int(camera), int(camera) + 1)
+
+    def _set_param(self, word: int, name: str, v, lo: int, hi: int, camera):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{name} = {v!r} outside {lo}..{hi}")
+        self._params[self._rows(camera), word] = v
+        if self.params is not self._params:
+            self.params.copy_(self._params)
+        return self
+
+    def set_min_cells(self, v: int, camera=None) -> "MotionRegions":
+        """Blobs of fewer cells are dropped."""
+        return self._set_param(0, "min_cells", v, 1, self.grid[0] * self.grid[1], camera)
+
+    def set_class(self, v: int, camera=None) -> "MotionRegions":
+        """The class written into the blob rows."""
+        return self._set_param(1, "class", v, 0, 65535, camera)
+
+    def set_ignore(self, camera, mask) -> "MotionRegions":
+        """``mask`` bool [GH, GW]: True = ignore the cell; with ``camera=None`` for every
+        camera, or bool [S, GH, GW] for all of them at once (one upload)."""
+        mask = torch.as_tensor(mask)
+        whole = camera is None and tuple(mask.shape) == (self.streams, *self.grid)
+        if mask.dtype != torch.bool or not (whole or tuple(mask.shape) == self.grid):
+            raise ValueError(f"the ignore mask is bool {list(self.grid)}, got {mask.dtype} "
+                             f"{tuple(mask.shape)}")
+        self._ignore[self._rows(camera)] = mask.cpu().to(torch.uint8)
+        if self.ignore is not self._ignore:
+            self.ignore.copy_(self._ignore)
+        return self
+
+    def rasterise(self, polygons) -> torch.Tensor:
+        """bool [GH, GW]: the cells whose centre lies in one of ``polygons`` (lists of 3 or
+        more pixel points), by the zones' crossing-number rule on quarter pixels."""
+        gh, gw = self.grid
+        py = ((2 * torch.arange(gh, dtype=torch.int64) + 1) * 2 * self.cell)[:, None].expand(gh, gw)
+        px = ((2 * torch.arange(gw, dtype=torch.int64) + 1) * 2 * self.cell)[None, :].expand(gh, gw)
+        hit = torch.zeros(gh, gw, dtype=torch.bool)
+        for poly in polygons:
+            poly = [tuple(_zone_q(p)) for p in poly]
+            if len(poly) < 3:
+                raise ValueError(f"an ignore polygon has 3 or more vertices, got {len(poly)}")
+            hit |= _ref.point_in_polygon(px, py, poly)
+        return hit
+
+    def set_ignore_polygons(self, camera, polygons) -> "MotionRegions":
+        """Ignore the cells of ``camera`` that :meth:`rasterise` finds under ``polygons``."""
+        return self.set_ignore(camera, self.rasterise(polygons))
+
+    def clear_ignore(self, camera=None) -> "MotionRegions":
+        return self.set_ignore(camera, torch.zeros(self.grid, dtype=torch.bool))
+
+
+def motion_blobs(mask: torch.Tensor, regions: MotionRegions, slot0: int = 0, max_blobs: int = 16,
+                 connectivity: int = 8, out_det: Optional[torch.Tensor] = None,
+                 out_count: Optional[torch.Tensor] = None,
+                 out_labels: Optional[torch.Tensor] = None):
+    """Motion regions of one step: camera n of ``mask`` -- uint8 [N, GH, GW], ops.frame_watch's
+    motion_mask -- is stream ``slot0 + n`` of ``regions``.  The moving cells that are not
+    ignored are grouped under 4- or 8-connectivity; of the blobs of at least min_cells cells
+    the ``max_blobs`` (1..64) largest are reported, ties by the lower first cell.  Returns
+    ``(blob_det, blob_count, labels)``: fp32 [N, max_blobs, 6] = the blob's pixel box x1, y1,
+    x2, y2, its cell count and the regions' class (rows from blob_count on all zero), int32
+    [N], and int32 [N, GH, GW], the cell's row in blob_det or -1.  Every element is written.
+    GPU (csrc/kernels/motion_blobs.hip) and CPU (ops.reference.motion_blobs, a flood fill) are
+    bit-identical."""
+    if not isinstance(regions, MotionRegions):
+        raise TypeError(f"regions must be an ops.MotionRegions, got {type(regions).__name__}")
+    if mask.dtype != torch.uint8 or mask.dim() != 3:
+        raise ValueError(f"mask must be uint8 [N, GH, GW], got {mask.dtype} {tuple(mask.shape)}")
+    if tuple(mask.shape[1:]) != regions.grid:
+        raise ValueError(f"mask grid {tuple(mask.shape[1:])}, the regions were made for "
+                         f"{regions.grid}")
+    if regions.grid[0] * regions.grid[1] > BLOB_MAX_CELLS:
+        raise ValueError(f"motion regions label at most {BLOB_MAX_CELLS} cells")
+    if not mask.is_contiguous():
+        raise ValueError("mask must be contiguous")
+    if mask.device != regions.device:
+        raise ValueError(f"mask on {mask.device}, regions on {regions.device}")
+    if isinstance(max_blobs, bool) or not 1 <= int(max_blobs) <= BLOB_MAX_BLOBS:
+        raise ValueError(f"max_blobs {max_blobs!r} outside 1..{BLOB_MAX_BLOBS}")
+    if connectivity not in BLOB_CONNECTIVITY:
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    n, R = int(mask.shape[0]), int(max_blobs)
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > regions.streams:
+        raise ValueError(f"streams [{slot0}, {slot0 + n}) outside the regions' {regions.streams}")
+    if out_det is None:
+        out_det = empty(n, R, 6, dtype=torch.float32, device=mask.device)
+    if out_count is None:
+        out_count = empty(n, dtype=torch.int32, device=mask.device)
+    if out_labels is None:
+        out_labels = empty(n, *regions.grid, dtype=torch.int32, device=mask.device)
+    for name, t, dt, shape in (("out_det", out_det, torch.float32, (n, R, 6)),
+                               ("out_count", out_count, torch.int32, (n,)),
+                               ("out_labels", out_labels, torch.int32, (n, *regions.grid))):
+        if (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != mask.device):
+            raise ValueError(f"{name} must be contiguous {dt} {list(shape)} on {mask.device}")
+    if mask.is_cuda:
+        _native().motion_blobs(mask, regions.params, regions.ignore, out_det, out_count,
+                               out_labels, slot0, regions.cell, *regions.frame_hw,
+                               int(connectivity))
+    else:
+        _ref.motion_blobs(mask, regions.params, regions.ignore, slot0, regions.cell,
+                          regions.frame_hw, int(connectivity), out_det, out_count, out_labels)
+    return out_det, out_count, out_labels
+
+
+# ---------------------------------------------------------------------------
 # camera snapshots: baseline JPEG files of frames that are already on the device
 # ---------------------------------------------------------------------------
 JPEG_SUBSAMPLINGS = _ref.JPEG_SUBSAMPLINGS

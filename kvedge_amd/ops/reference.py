@@ -1082,3 +1082,76 @@ def annotate(images, table, font, det=None, count=None, track_id=None, src_hw=No
                             lab[yy:yy + s, xx:xx + s] = ink
             img[y0:y0 + lh, x0:x0 + lw] = lab[:h - y0, :w - x0]
     return images
+
+
+# ---------------------------------------------------------------------------
+# motion regions: the watch's motion grid -> connected blobs as detection rows
+# ---------------------------------------------------------------------------
+BLOB_MAX_CELLS = 32768
+BLOB_MAX_BLOBS = 64
+BLOB_CLASS = 80  # one past COCO: class filters keep blobs apart from detections
+
+
+def blob_components(active, connectivity):
+    """Components of a bool [GH, GW] grid under 4- or 8-connectivity by flood fill, in raster
+    order of their first cell: a list of cell lists [(y, x), ...]."""
+    gh, gw = active.shape
+    todo = active.tolist()
+    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)]
+    if connectivity == 8:
+        steps += [(-1, -1), (-1, 1), (1, -1), (1, 1)]
+    out = []
+    for y0 in range(gh):
+        for x0 in range(gw):
+            if not todo[y0][x0]:
+                continue
+            todo[y0][x0] = False
+            cells, stack = [], [(y0, x0)]
+            while stack:
+                y, x = stack.pop()
+                cells.append((y, x))
+                for dy, dx in steps:
+                    v, u = y + dy, x + dx
+                    if 0 <= v < gh and 0 <= u < gw and todo[v][u]:
+                        todo[v][u] = False
+                        stack.append((v, u))
+            out.append(cells)
+    return out
+
+
+def motion_blobs(mask, params, ignore, slot0, cell, frame_hw, connectivity, out_det, out_count,
+                 out_labels):
+    """Motion regions: THE definition the HIP kernel (csrc/kernels/motion_blobs.hip) equals bit
+    for bit.  ``mask`` uint8 [N, GH, GW] (ops.frame_watch's motion_mask), ``params`` int32
+    [S, 4] = min_cells, cls, 0, 0 and ``ignore`` uint8 [S, GH, GW]; camera n is stream
+    ``slot0 + n``; ``frame_hw`` = (Hs, Ws) pixels cut into ``cell``-pixel cells.
+
+    A cell is active when (mask & 1) != 0 and ignore == 0.  Active cells are grouped under
+    ``connectivity`` 4 or 8; a component has n cells, the inclusive cell box cx0 cy0 cx1 cy1 and
+    first, its smallest y * GW + x.  Components of n >= min_cells (clamped into 1..GH GW) are
+    kept and ordered by n descending, then first ascending; the first R = out_det.shape[1] are
+    reported: out_count = min(kept, R); out_det[n, r] = (cx0 cell, cy0 cell,
+    min((cx1 + 1) cell, Ws), min((cy1 + 1) cell, Hs), n, cls) with cls clamped into 0..65535,
+    rows from out_count on all zero; out_labels int32 [N, GH, GW] = r on the cells of reported
+    blob r and -1 on every other cell."""
+    hs, ws = int(frame_hw[0]), int(frame_hw[1])
+    R = int(out_det.shape[1])
+    out_det.zero_()
+    out_labels.fill_(-1)
+    for n in range(mask.shape[0]):
+        s = slot0 + n
+        gh, gw = mask.shape[1], mask.shape[2]
+        min_cells = min(max(int(params[s, 0]), 1), gh * gw)
+        cls = min(max(int(params[s, 1]), 0), 65535)
+        active = ((mask[n] & 1) != 0) & (ignore[s] == 0)
+        # flood fill visits components by ascending first; the stable sort keeps that on ties
+        kept = [c for c in blob_components(active, connectivity) if len(c) >= min_cells]
+        kept.sort(key=len, reverse=True)
+        out_count[n] = min(len(kept), R)
+        for r, cells in enumerate(kept[:R]):
+            ys, xs = [c[0] for c in cells], [c[1] for c in cells]
+            out_det[n, r] = torch.tensor(
+                [min(xs) * cell, min(ys) * cell, min((max(xs) + 1) * cell, ws),
+                 min((max(ys) + 1) * cell, hs), len(cells), cls], dtype=torch.float32)
+            out_labels[n][torch.tensor(ys), torch.tensor(xs)] = r
+    return out_det, out_count, out_labels
