@@ -325,8 +325,9 @@ __global__ __launch_bounds__(kBlock) void upsample2x_kernel(const bf16* __restri
     const int w = pix % W;
     const int nh = pix / W;              // n*H + h
     const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + (long long)pix * ldx + x_coff + c8 * 8);
-    // output row n*Ho + 2h = 2*nh, columns 2w and 2w+1
-    bf16* r0 = y + ((long long)(2 * nh) * Wo + 2 * w) * ldy + y_coff + c8 * 8;
+    // output row n*Ho + 2h = 2*nh, columns 2w and 2w+1.  64-bit from the first product: at
+    // W = 1, C = 8 the item rule admits nh up to 2^31 - 2^21, and 2 * nh does not fit an int
+    bf16* r0 = y + (2ll * nh * Wo + 2 * w) * ldy + y_coff + c8 * 8;
     bf16* r1 = r0 + (long long)Wo * ldy;
     *reinterpret_cast<bf16x8*>(r0) = v;
     *reinterpret_cast<bf16x8*>(r0 + ldy) = v;
@@ -510,6 +511,7 @@ extern "C" int kv_global_avgpool(const void* x, void* y, int N, int HW, int C, h
 extern "C" int kv_pooled_fc(const void* x, int N, int HW, int C, const void* w, int ldw,
                             const float* bias, void* y, int ncls, hipStream_t s) {
   if (N <= 0 || C % 8 || ldw < C || ldw % 8 || C > 16384) return -1;
+  if (N > 65535) return -2;  // grid y
   // pixel split of the pooling pass: enough (channel chunk, part) items for the 512 threads,
   // while the [split][C] fp32 partials fit in 64 KB of LDS
   int split = 1;
