@@ -690,6 +690,69 @@ void det_to_source(at::Tensor& det, const at::Tensor& count, at::ArrayRef<double
   TORCH_CHECK(rc == 0, "kvedge: det_to_source failed rc=", rc);
 }
 
+// K24: per-camera mesh warp (csrc/kernels/frame_warp.hip); mesh i32 [streams,Hd/16+1,Wd/16+1,2]
+// and pad i32 [streams] are an ops.CameraViews' tensors, batch row n is stream slot0 + n.
+// nv12: src u8 [N, Hs*3/2, Ws].  Geometry is left to the launcher, whose codes the tests read.
+void frame_warp(const at::Tensor& src, at::Tensor& dst, const at::Tensor& mesh,
+                const at::Tensor& pad, int64_t slot0, bool nv12) {
+  check_dev(src, "src");
+  check_dev(dst, "dst");
+  check_dev(mesh, "mesh");
+  check_dev(pad, "pad");
+  TORCH_CHECK(src.scalar_type() == at::kByte &&
+                  (nv12 ? src.dim() == 3 && src.size(1) % 3 == 0
+                        : src.dim() == 4 && src.size(3) == 3),
+              "kvedge: src u8 [N,Hs,Ws,3], or NV12 [N,Hs*3/2,Ws]");
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.dim() == 4 && dst.size(3) == 3 &&
+                  dst.size(0) == src.size(0), "kvedge: dst u8 [N,Hd,Wd,3]");
+  TORCH_CHECK(mesh.scalar_type() == at::kInt && mesh.dim() == 4 && mesh.size(3) == 2,
+              "kvedge: mesh i32 [streams,Gy,Gx,2]");
+  TORCH_CHECK(pad.scalar_type() == at::kInt && pad.dim() == 1 && pad.size(0) == mesh.size(0),
+              "kvedge: pad i32 [streams]");
+  const int64_t lim = 1 << 20;
+  TORCH_CHECK(src.size(0) < lim && src.size(1) < lim && src.size(2) < lim && dst.size(1) < lim &&
+                  dst.size(2) < lim && mesh.size(0) < lim && mesh.size(1) < lim &&
+                  mesh.size(2) < lim && slot0 >= -lim && slot0 < lim,
+              "kvedge: frame_warp sizes out of range");
+  TORCH_CHECK(src.device() == dst.device() && src.device() == mesh.device() &&
+                  src.device() == pad.device(), "kvedge: frame_warp operands on different devices");
+  const int Hs = (int)(nv12 ? src.size(1) / 3 * 2 : src.size(1));
+  const c10::DeviceGuard g(src.device());
+  const int rc = (nv12 ? kv_frame_warp_nv12 : kv_frame_warp)(
+      src.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(), mesh.data_ptr<int>(), pad.data_ptr<int>(),
+      (int)src.size(0), Hs, (int)src.size(2), (int)dst.size(1), (int)dst.size(2),
+      (int)mesh.size(0), (int)mesh.size(1), (int)mesh.size(2), (int)slot0, cur_stream(src));
+  TORCH_CHECK(rc == 0, "kvedge: frame_warp failed rc=", rc);
+}
+
+// K25: kept boxes from view pixels back to source-frame pixels through the mesh, in place
+void view_to_source(at::Tensor& det, const at::Tensor& count, const at::Tensor& mesh, int64_t Hs,
+                    int64_t Ws, int64_t Hd, int64_t Wd, int64_t slot0) {
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(mesh, "mesh");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6,
+              "kvedge: det fp32 [N,max_det,6]");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == det.size(0),
+              "kvedge: count int32 [N]");
+  TORCH_CHECK(mesh.scalar_type() == at::kInt && mesh.dim() == 4 && mesh.size(3) == 2,
+              "kvedge: mesh i32 [streams,Gy,Gx,2]");
+  const int64_t lim = 1 << 20;
+  TORCH_CHECK(det.size(0) < lim && det.size(1) < lim && mesh.size(0) < lim && mesh.size(1) < lim &&
+                  mesh.size(2) < lim && slot0 >= -lim && slot0 < lim && Hs >= 0 && Hs < lim &&
+                  Ws >= 0 && Ws < lim && Hd >= 0 && Hd < lim && Wd >= 0 && Wd < lim,
+              "kvedge: view_to_source sizes out of range");
+  TORCH_CHECK(det.device() == count.device() && det.device() == mesh.device(),
+              "kvedge: view_to_source operands on different devices");
+  const c10::DeviceGuard g(det.device());
+  const int rc = kv_view_to_source(det.data_ptr<float>(), count.data_ptr<int>(),
+                                   mesh.data_ptr<int>(), (int)det.size(0), (int)det.size(1),
+                                   (int)Hs, (int)Ws, (int)Hd, (int)Wd, (int)mesh.size(0),
+                                   (int)mesh.size(1), (int)mesh.size(2), (int)slot0,
+                                   cur_stream(det));
+  TORCH_CHECK(rc == 0, "kvedge: view_to_source failed rc=", rc);
+}
+
 // K15: top-K detection boxes -> fixed-size uint8 crops (csrc/kernels/roi_crop.hip); K and D
 // are dst's shape.  band: destination rows per workgroup, 0 = the built-in choice.
 void roi_crop_band(const at::Tensor& src, const at::Tensor& det, const at::Tensor& count,
@@ -1252,6 +1315,10 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("preprocess(Tensor x, Tensor(a!) y, float[] mean, float[] std) -> ()");
   m.def("frame_resize(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
   m.def("det_to_source(Tensor(a!) det, Tensor count, float[] map, int Hs, int Ws) -> ()");
+  m.def("frame_warp(Tensor src, Tensor(a!) dst, Tensor mesh, Tensor pad, int slot0, bool nv12) "
+        "-> ()");
+  m.def("view_to_source(Tensor(a!) det, Tensor count, Tensor mesh, int Hs, int Ws, int Hd, int Wd, "
+        "int slot0) -> ()");
   m.def("roi_crop(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad) -> ()");
   m.def("roi_crop_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
   m.def("frame_resize_nv12(Tensor src, Tensor(a!) dst, int[] axis_y, int[] axis_x, int pad) -> ()");
@@ -1309,6 +1376,8 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("yolo_stem2", yolo_stem2);
   m.impl("frame_resize", frame_resize);
   m.impl("det_to_source", det_to_source);
+  m.impl("frame_warp", frame_warp);
+  m.impl("view_to_source", view_to_source);
   m.impl("roi_crop", roi_crop);
   m.impl("roi_crop_band", roi_crop_band);
   m.impl("frame_resize_nv12", frame_resize_nv12);

@@ -189,6 +189,26 @@ int kv_roi_crop_nv12(const uint8_t* src, const float* det, const int* count, uin
 int kv_roi_crop_nv12_band(const uint8_t* src, const float* det, const int* count, uint8_t* dst,
                           int N, int Hs, int Ws, int max_det, int K, int D, int pad, int band,
                           hipStream_t s);
+// K24 (frame_warp.hip): per-camera mesh warp of native frames src u8 [N,Hs,Ws,3] (_nv12: NV12
+// [N,Hs*3/2,Ws]) into dst u8 [N,Hd,Wd,3].  mesh int32 [streams,gy,gx,2], gy = Hd/16 + 1,
+// gx = Wd/16 + 1: node (y, x) is the source position, in 1/64 pixel and pixel-corner
+// coordinates, that destination point (16 x, 16 y) samples; pad int32 [streams]; batch row n
+// uses stream slot0 + n.  The sampling rule is at the top of frame_warp.hip; bit-identical to
+// ops.reference.frame_warp; every destination byte is written.  Hd % 16 == Wd % 16 == 0,
+// extents 1..8192.
+// Returns -1 Hd / Wd % 16, -2 extents or N, -3 mesh shape, -4 slot0 + N > streams, -5 misaligned
+// dst, -6 misaligned mesh / pad, -8 odd NV12 size, -9 odd NV12 address.
+int kv_frame_warp(const uint8_t* src, uint8_t* dst, const int* mesh, const int* pad, int N, int Hs,
+                  int Ws, int Hd, int Wd, int streams, int gy, int gx, int slot0, hipStream_t s);
+int kv_frame_warp_nv12(const uint8_t* src, uint8_t* dst, const int* mesh, const int* pad, int N,
+                       int Hs, int Ws, int Hd, int Wd, int streams, int gy, int gx, int slot0,
+                       hipStream_t s);
+// K25: kept boxes det fp32 [N,max_det,6] (rows < count[n]) from the view's Hd x Wd pixels back
+// to source-frame pixels through the same mesh, in place: the hull of the four corners and four
+// edge midpoints (bit-identical to ops.reference.view_to_source).  Codes as K24's.
+int kv_view_to_source(float* det, const int* count, const int* mesh, int N, int max_det, int Hs,
+                      int Ws, int Hd, int Wd, int streams, int gy, int gx, int slot0,
+                      hipStream_t s);
 // K18 (track.hip): one IoU-tracker update of streams [slot0, slot0 + N) of state int32
 // [S, kv_track_state_stride(T)] from the step's detections det fp32 [N,max_det,6] / count
 // int32 [N] (batch row n is the next frame of stream slot0 + n); track_id int32 [N,max_det]

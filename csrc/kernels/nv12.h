@@ -15,17 +15,21 @@
 
 namespace kvedge {
 
+// one (Y, UV pair) sample -> RGB; uv = U | V << 8 as the 16-bit load delivers it
+__device__ __forceinline__ void nv12_rgb(int y, unsigned uv, int& r, int& g, int& b) {
+  const int c = 298 * (y - 16) + 128;
+  const int d = (int)(uv & 0xffu) - 128, e = (int)(uv >> 8) - 128;
+  r = min(max((c + 409 * e) >> 8, 0), 255);
+  g = min(max((c - 100 * d - 208 * e) >> 8, 0), 255);
+  b = min(max((c + 516 * d) >> 8, 0), 255);
+}
+
 // one tap: y_row / uv_row point at the tap's Y row and chroma row, q is its pixel column.
 // The pair is one 16-bit load: uv_row and q & ~1 are even (even frame address, even Ws).
 __device__ __forceinline__ void nv12_tap(const uint8_t* __restrict__ y_row,
                                          const uint8_t* __restrict__ uv_row, int q, int& r,
                                          int& g, int& b) {
-  const int c = 298 * ((int)y_row[q] - 16) + 128;
-  const unsigned uv = *reinterpret_cast<const uint16_t*>(uv_row + (q & ~1));
-  const int d = (int)(uv & 0xffu) - 128, e = (int)(uv >> 8) - 128;
-  r = min(max((c + 409 * e) >> 8, 0), 255);
-  g = min(max((c - 100 * d - 208 * e) >> 8, 0), 255);
-  b = min(max((c + 516 * d) >> 8, 0), 255);
+  nv12_rgb((int)y_row[q], *reinterpret_cast<const uint16_t*>(uv_row + (q & ~1)), r, g, b);
 }
 
 }  // namespace kvedge

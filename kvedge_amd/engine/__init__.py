@@ -80,6 +80,11 @@ class InferenceEngine:
     decoders deliver them, ``source_frames`` is [B, Hs * 3 // 2, Ws] (half the bytes through
     the ring and over PCIe) and the resample converts each source tap to RGB on the way
     (ops.frame_resize(..., src_format="nv12")).  NV12 needs ``frame_hw``.
+    views: an ops.CameraViews with one view per batch row (ROI, rotation, lens dewarp,
+    perspective): the front end is then ops.frame_warp in place of the resize, and the boxes go
+    back to frame pixels through the same meshes (ops.view_to_source), so everything after the
+    model still sees native-frame pixels.  The meshes live in device memory outside the graph:
+    ``views.set`` changes a camera's view from the next step, no recapture.  Needs ``frame_hw``.
     A model with ``stateful = True`` (models.tracking.KvTracked) keeps device state across steps,
     one entry per batch row: it is called with ``slot0`` = the first batch row of the slice, its
     state is left freshly reset by ``prepare()`` (``reset_tracks()`` does the same later), and
@@ -89,7 +94,7 @@ class InferenceEngine:
     def __init__(self, model: Callable, batch: int, image_size: int, device="cuda",
                  seed: int = 0, use_graph: bool = True, synthetic: bool = True,
                  streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None,
-                 frame_format: str = "rgb"):
+                 frame_format: str = "rgb", views: Optional["ops.CameraViews"] = None):
         if frame_format not in ops.SRC_FORMATS:
             raise ValueError(f"frame_format must be one of {ops.SRC_FORMATS}, "
                              f"got {frame_format!r}")
@@ -125,6 +130,17 @@ class InferenceEngine:
             self.frame_plan = model.frame_plan(self.frame_hw, image_size)
             shape = (batch, hs * 3 // 2, ws) if nv12 else (batch, hs, ws, 3)
             self.source_frames = torch.empty(*shape, dtype=torch.uint8, device=self.device)
+        self.views = views
+        if views is not None:
+            if not isinstance(views, ops.CameraViews):
+                raise TypeError(f"views must be an ops.CameraViews, got {type(views).__name__}")
+            if self.frame_hw is None:
+                raise ValueError("views need the size of the incoming frames (frame_hw)")
+            want = (batch, self.frame_hw, (image_size, image_size), self.device.type)
+            have = (views.streams, views.src_hw, views.dst_hw, views.device.type)
+            if want != have:
+                raise ValueError(f"views are (cameras, frame, model size, device) = {have}, the "
+                                 f"engine needs {want}")
         # [step counter, finished-block count]: synth_frames bumps it in-kernel (one launch)
         self.step_ctr = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.outputs = None
@@ -165,13 +181,19 @@ class InferenceEngine:
         # the format keyword only where it is not the default: models and plans written
         # before NV12 keep their call signatures
         fmt = {} if self.frame_format == "rgb" else {"src_format": self.frame_format}
-        ops.frame_resize(self.source_frames[lo:hi], self.frame_plan, out=frames, **fmt)
+        plan = self.frame_plan
+        if self.views is None:
+            ops.frame_resize(self.source_frames[lo:hi], plan, out=frames, **fmt)
+        else:
+            # the models hand ``plan`` to ops.det_to_source, which maps through the meshes
+            ops.frame_warp(self.source_frames[lo:hi], self.views, out=frames, slot0=lo, **fmt)
+            plan = ops.ViewSlots(self.views, lo)
         if hasattr(self.model, "from_source"):
-            return self.model.from_source(self.source_frames[lo:hi], frames, self.frame_plan,
+            return self.model.from_source(self.source_frames[lo:hi], frames, plan,
                                           **self._slot(lo), **fmt)
         out = self.model(frames, **self._slot(lo))
         if hasattr(self.model, "to_source"):
-            out = self.model.to_source(out, self.frame_plan)
+            out = self.model.to_source(out, plan)
         return out
 
     def _slot(self, lo: int) -> dict:

@@ -32,6 +32,14 @@ def _process_start_epoch():
         return None
 
 
+def _json_arg(v: str) -> str:
+    """A JSON command-line value: the text of the file it names, else the value itself."""
+    if v and os.path.isfile(v):
+        with open(v) as f:
+            return f.read()
+    return v
+
+
 def _topology_from_env() -> int:
     """Map the chart's per-VM env (KVEDGE_NODE_RANK / KVEDGE_NNODES /
     KVEDGE_RANKS_PER_NODE, deploy/helm/templates/kvedge-module-deployment.yaml) to
@@ -101,6 +109,12 @@ def main(argv=None):
                     help="--track: polygon zones, inline JSON '[{\"name\": ..., \"polygon\": "
                          "[[x, y], ...], \"class\"?, \"cameras\"?}]' (at most 8, 3..8 vertices; "
                          "telemetry gains `zones`)")
+    ap.add_argument("--views-json", default="",
+                    help="per-camera views (need --frame-height / --frame-width): a JSON file, or "
+                         "inline JSON, holding a list with one entry per camera, each null or "
+                         "'{\"roi\": [x0, y0, x1, y1], \"rotate\": 0|90|180|270, \"mirror\", "
+                         "\"homography\": 3x3, \"lens\": {...}, \"pad\"}' (twin key `views`, "
+                         "live)")
     ap.add_argument("--zone-anchor", default=d.zone_anchor, choices=["bottom", "centre"],
                     help="the point of a box tested against lines and zones")
     ap.add_argument("--watch", action="store_true",
@@ -200,7 +214,8 @@ def main(argv=None):
                        track_iou=a.track_iou, track_max_age=a.track_max_age,
                        track_min_hits=a.track_min_hits,
                        track_max_tracks=a.track_max_tracks, lines=a.lines_json,
-                       zones=a.zones_json, zone_anchor=a.zone_anchor, watch=a.watch,
+                       zones=a.zones_json, views=_json_arg(a.views_json),
+                       zone_anchor=a.zone_anchor, watch=a.watch,
                        watch_cell=a.watch_cell, watch_row_step=a.watch_row_step,
                        watch_bg_shift=a.watch_bg_shift,
                        watch_motion_level=a.watch_motion_level,

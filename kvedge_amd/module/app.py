@@ -202,6 +202,7 @@ class ModuleApp:
         self.zone_totals = None  # module.zones.ZoneTotals once lines / zones are configured
         self.camera_totals = None  # module.watch.CameraTotals with `watch` on
         self.snapshots = None  # module.snapshots.SnapshotSender with `snapshots` on
+        self.views = None  # ops.CameraViews with `views` configured
         self.ring = None
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
@@ -405,6 +406,7 @@ class ModuleApp:
         self.zone_totals = None
         self.camera_totals = None
         self.snapshots = None
+        self.views = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -473,13 +475,20 @@ class ModuleApp:
                                    max_blobs=cfg.watch_region_max,
                                    connectivity=cfg.watch_region_connectivity,
                                    **cfg.watch_params())
+        self.views = None
+        if cfg.views:  # per-camera meshes in device memory: the front end is ops.frame_warp
+            size = cfg.resolved_image_size()
+            self.views = ops.CameraViews(cfg.batch, cfg.frame_hw(), (size, size), dev,
+                                         fit=cfg.view_fit())
+            self._apply_views(cfg)
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
                                       seed=cfg.seed + self.rank, use_graph=cfg.use_graph,
                                       synthetic=not camera,
                                       streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1,
-                                      frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format())
+                                      frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format(),
+                                      views=self.views)
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
@@ -534,7 +543,7 @@ class ModuleApp:
         err = next((e for e in errs if e), None)
         if err is not None:
             self.engine = self.model = self.zone_totals = self.camera_totals = None
-            self.sim = self.snapshots = None
+            self.sim = self.snapshots = self.views = None
             self._stop_camera()
             if previous is None:
                 return err
@@ -841,6 +850,15 @@ class ModuleApp:
         self._events.append(("twin", dict(patch or {})))
         self._replies.append(None)
 
+    def _apply_views(self, cfg: ModuleConfig) -> None:
+        """``cfg.views`` into the device meshes; cameras past the list get the plain view."""
+        meshes = cfg.view_meshes()
+        for cam in range(cfg.batch):
+            if cam < len(meshes):
+                self.views.set(cam, *meshes[cam])
+            else:
+                self.views.set_view(cam, None)
+
     def _apply_patch(self, patch: Dict[str, Any]) -> Tuple[int, Dict[str, Any]]:
         try:
             new = self.cfg.apply_patch(patch)
@@ -862,6 +880,10 @@ class ModuleApp:
             from .watch import apply_motion_regions
 
             apply_motion_regions(self.model.regions, self.cfg)
+        if (self.views is not None and not self.cfg.needs_rebuild(old)
+                and self.cfg.views != old.views):
+            # the view meshes too: the next replay warps through the new ones
+            self._apply_views(self.cfg)
         if (self.snapshots is not None and not self.cfg.needs_rebuild(old)
                 and self.cfg.snapshot_quality != old.snapshot_quality):
             # the quantisation tables live in device memory, like the watch thresholds

@@ -92,6 +92,22 @@ def _ignore_zones(v) -> Tuple[Dict[str, Any], ...]:
                  for r in _regions(v, "watch_ignore"))
 
 
+def _views(v) -> Tuple[Any, ...]:
+    """The ``views`` twin key: a list (or the same as JSON text) with one entry per camera,
+    each null (the plain letterbox / centre-crop) or an object {roi, rotate, mirror, homography,
+    lens, pad} (ops.view_mesh); the entries themselves are checked by ``validate``."""
+    if isinstance(v, str):
+        v = json.loads(v) if v.strip() else []
+    if v is None:
+        v = []
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"views must be a list with one entry per camera, got {type(v).__name__}")
+    for i, r in enumerate(v):
+        if r is not None and not isinstance(r, dict):
+            raise ValueError(f"views[{i}] must be an object or null, got {r!r}")
+    return tuple(None if r is None else dict(r) for r in v)
+
+
 def _int_tuple(v, what: str) -> Tuple[int, ...]:
     """A list of integers, or the same as "0,2" / JSON text."""
     if isinstance(v, str):
@@ -158,6 +174,12 @@ class ModuleConfig:
     # zone_anchor: the point of a box that is tested, "bottom" (bottom-centre) or "centre"
     lines: Tuple[Dict[str, Any], ...] = ()
     zones: Tuple[Dict[str, Any], ...] = ()
+    # per-camera views (they need frame_height / frame_width): one entry per camera, null or
+    # {roi: [x0, y0, x1, y1], rotate: 0|90|180|270, mirror, homography: 3 x 3, lens: {fx, fy, cx,
+    # cy, k1, k2, p1, p2, k3} | {fisheye: {f, cx, cy, fov}}, pad}.  The front end is then the
+    # mesh warp (ops.frame_warp) and boxes stay in frame pixels.  Live: the meshes are device
+    # memory the captured step reads, so a change needs no rebuild (switching views on or off does)
+    views: Tuple[Any, ...] = ()
     zone_anchor: str = "bottom"
     # per-camera frame watch (ops.frame_watch): one more streaming pass over the incoming
     # frames, one batch row = one camera.  A motion grid of watch_cell-pixel cells against a
@@ -245,6 +267,7 @@ class ModuleConfig:
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
             object.__setattr__(self, kind, _regions(getattr(self, kind), kind))
+        object.__setattr__(self, "views", _views(self.views))
         object.__setattr__(self, "snapshot_privacy_zones",
                            _privacy_zones(self.snapshot_privacy_zones))
         object.__setattr__(self, "watch_ignore", _ignore_zones(self.watch_ignore))
@@ -320,6 +343,14 @@ class ModuleConfig:
                                      f"{len(r['polygon'])}")
         if (self.lines or self.zones) and not self.track:
             raise ValueError("lines / zones count tracked objects: they need track true")
+        if self.views:
+            if not self.frame_height:
+                raise ValueError("views need frame_height and frame_width")
+            if self.model == "simulated-temperature":
+                raise ValueError("views need frames: a vision model")
+            if len(self.views) > self.batch:
+                raise ValueError(f"views has {len(self.views)} entries for {self.batch} cameras")
+            self.view_meshes()  # ops.view_mesh's ValueErrors, with the entry's index
         # the frame-watch launcher's ranges (csrc/kernels/frame_watch.hip)
         if self.watch_cell not in (8, 16, 32):
             raise ValueError("watch_cell must be 8, 16 or 32")
@@ -442,6 +473,8 @@ class ModuleConfig:
                 v = _int_tuple(v, k)
             elif k == "watch_ignore":
                 v = _ignore_zones(v)
+            elif k == "views":
+                v = _views(v)
             elif isinstance(cur, tuple):
                 v = _regions(v, k)
             else:
@@ -450,7 +483,26 @@ class ModuleConfig:
         return replace(self, **kw).validate()
 
     def needs_rebuild(self, other: "ModuleConfig") -> bool:
-        return any(getattr(self, k) != getattr(other, k) for k in self.REBUILD)
+        # views: only switching them on or off changes the captured step
+        return (any(getattr(self, k) != getattr(other, k) for k in self.REBUILD)
+                or bool(self.views) != bool(other.views))
+
+    def view_fit(self) -> str:
+        """How a plain view fills the model frame: the model's own front end."""
+        return "crop" if self.model == "resnet50" else "letterbox"
+
+    def view_meshes(self):
+        """[(mesh, pad)] of ``views``, one per listed camera (ops.view_mesh_from)."""
+        from ..ops import view_mesh_from
+
+        size = self.resolved_image_size()
+        out = []
+        for i, v in enumerate(self.views):
+            try:
+                out.append(view_mesh_from(self.frame_hw(), (size, size), v, self.view_fit()))
+            except ValueError as e:
+                raise ValueError(f"views[{i}]: {e}") from None
+        return out
 
     def resolved_image_size(self) -> int:
         if self.image_size:
@@ -517,6 +569,11 @@ class ModuleConfig:
                 d.pop(k)
         else:
             d["lines"], d["zones"] = list(d["lines"]), list(d["zones"])
+        # and the views
+        if self.views:
+            d["views"] = list(d["views"])
+        else:
+            d.pop("views")
         # and the frame-watch keys
         if all(getattr(self, k) == getattr(base, k) for k in self.WATCH_KEYS):
             for k in self.WATCH_KEYS:

@@ -867,12 +867,319 @@ def det_to_source(det: torch.Tensor, count: torch.Tensor, plan: ResizePlan) -> t
     """Kept boxes of :func:`nms` (det fp32 [N, max_det, 6], rows < count[n]) from model
     coordinates to source-frame pixels, in place: x = clamp((x - cx) * sx, 0, Ws),
     y = clamp((y - cy) * sy, 0, Hs).  Score, class and the rows past count are untouched."""
+    if isinstance(plan, ViewSlots):  # per-camera views: through the mesh
+        return view_to_source(det, count, plan.views, plan.slot0)
     cy, sy, cx, sx = plan.box_map()
     hs, ws = plan.src_hw
     if det.is_cuda:
         _native().det_to_source(det, count, [cy, sy, cx, sx], hs, ws)
     else:
         _ref.det_to_source(det, count, (cy, sy, cx, sx), hs, ws)
+    return det
+
+
+# ---------------------------------------------------------------------------
+# per-camera views: a mesh-driven warp (ROI, rotation, lens dewarp, perspective)
+# ---------------------------------------------------------------------------
+VIEW_CELL = 16           # destination pixels per mesh cell
+VIEW_NODE_LIM = 1 << 20  # node values are clamped to [-2^20, 2^20): 1/64 source pixel
+VIEW_FITS = ("letterbox", "stretch", "crop")
+VIEW_KEYS = ("roi", "rotate", "mirror", "homography", "lens", "pad")
+_LENS_KEYS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+_FISHEYE_KEYS = ("f", "cx", "cy", "fov")
+
+
+def _check_view_hw(src_hw, dst_hw):
+    (hs, ws), (hd, wd) = (int(src_hw[0]), int(src_hw[1])), (int(dst_hw[0]), int(dst_hw[1]))
+    if not (1 <= hs <= RESIZE_MAX_EXTENT and 1 <= ws <= RESIZE_MAX_EXTENT):
+        raise ValueError(f"frame size {hs}x{ws} outside 1..{RESIZE_MAX_EXTENT}")
+    if not (1 <= hd <= RESIZE_MAX_EXTENT and 1 <= wd <= RESIZE_MAX_EXTENT):
+        raise ValueError(f"view size {hd}x{wd} outside 1..{RESIZE_MAX_EXTENT}")
+    if hd % VIEW_CELL or wd % VIEW_CELL:
+        raise ValueError(f"view size {hd}x{wd} must be a multiple of {VIEW_CELL} in both axes")
+    return (hs, ws), (hd, wd)
+
+
+def _fit_axis(fit: str, d: int, view: float, scale: float):
+    """One axis of the view rectangle (``view`` long) inside ``d`` destination pixels: (first
+    destination coordinate that holds it, view units per destination pixel)."""
+    if fit == "stretch":
+        return 0.0, view / d
+    if fit == "crop":  # scale = the resized extent of this axis (center_crop_plan)
+        return -float(int(round((scale - d) / 2))), view / scale
+    n = min(d, max(1, int(round(view * scale))))  # letterbox_plan's rounding
+    return float(int(round((d - n) / 2 - 0.1))), view / n
+
+
+def _lens_points(x, y, lens, ws: int):
+    """Ideal (rectilinear) source positions -> positions in the camera's distorted frame,
+    both in pixel-corner coordinates; the models themselves use OpenCV's pixel centres."""
+    import numpy as np
+
+    if not isinstance(lens, dict):
+        raise ValueError(f"lens must be an object, got {type(lens).__name__}")
+    fish = lens.get("fisheye")
+    keys, src = (_FISHEYE_KEYS, fish) if fish is not None else (_LENS_KEYS, lens)
+    if not isinstance(src, dict) or (fish is not None and len(lens) != 1):
+        raise ValueError('a fisheye lens is {"fisheye": {"f", "cx", "cy", "fov"}}')
+    unknown = sorted(set(src) - set(keys))
+    if unknown:
+        raise ValueError(f"unknown lens keys {unknown}; known: {keys}")
+    p = {}
+    for k in keys:
+        v = src.get(k, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"lens {k} = {v!r} is not a finite number")
+        p[k] = float(v)
+    x, y = x - 0.5, y - 0.5
+    if fish is not None:
+        if p["f"] <= 0 or not 0 < p["fov"] < 180:
+            raise ValueError("fisheye needs f > 0 and 0 < fov < 180 (degrees)")
+        # the ideal view is a pinhole that sees ``fov`` degrees across the frame width;
+        # equidistant: the distorted radius is f * (angle from the axis)
+        fp = (ws / 2) / np.tan(np.radians(p["fov"]) / 2)
+        xr, yr = x - p["cx"], y - p["cy"]
+        r = np.hypot(xr, yr)
+        k = np.where(r > 1e-9, p["f"] * np.arctan(r / fp) / np.maximum(r, 1e-9), p["f"] / fp)
+        return p["cx"] + xr * k + 0.5, p["cy"] + yr * k + 0.5
+    if p["fx"] <= 0 or p["fy"] <= 0:
+        raise ValueError("lens needs fx > 0 and fy > 0")
+    xn, yn = (x - p["cx"]) / p["fx"], (y - p["cy"]) / p["fy"]
+    r2 = xn * xn + yn * yn
+    rad = 1 + r2 * (p["k1"] + r2 * (p["k2"] + r2 * p["k3"]))
+    xd = xn * rad + 2 * p["p1"] * xn * yn + p["p2"] * (r2 + 2 * xn * xn)
+    yd = yn * rad + p["p1"] * (r2 + 2 * yn * yn) + 2 * p["p2"] * xn * yn
+    return p["fx"] * xd + p["cx"] + 0.5, p["fy"] * yd + p["cy"] + 0.5
+
+
+def view_mesh(src_hw, dst_hw, *, roi=None, rotate: int = 0, mirror: bool = False,
+              homography=None, lens=None, fit: str = "letterbox"):
+    """The mesh of one camera view (:class:`CameraViews`): int32 numpy [Hd/16 + 1, Wd/16 + 1, 2],
+    node (gy, gx) = the source position (x, y), in 1/64 pixel and pixel-corner coordinates,
+    that destination point (16 gx, 16 gy) samples.  Computed in float64 and rounded once.
+    From the destination to the source it composes: the inverse of ``fit`` ("letterbox": the
+    view rectangle scaled uniformly into the destination and centred with
+    :func:`letterbox_plan`'s rounding; "crop": :func:`center_crop_plan`'s resize and centre
+    crop, square destinations; "stretch"); ``mirror`` (left-right, of the view) and ``rotate``
+    (0 / 90 / 180 / 270: the view is the source turned counter-clockwise, ``np.rot90``);
+    ``roi`` = (x0, y0, x1, y1), the source rectangle the view shows (digital zoom; default the
+    whole frame; the letterbox bars show what the frame holds beyond it); ``homography``, 3 x 3,
+    ideal source position -> source position; ``lens``, ideal -> distorted position: Brown-Conrady
+    in OpenCV's convention {fx, fy, cx, cy, k1, k2, p1, p2, k3} or an equidistant fisheye
+    {"fisheye": {f, cx, cy, fov}} seen as a pinhole of ``fov`` degrees across the frame width.
+    With no options the mesh reproduces :func:`frame_resize` with the corresponding plan
+    (exactly where the scale is an integer ratio)."""
+    import numpy as np
+
+    (hs, ws), (hd, wd) = _check_view_hw(src_hw, dst_hw)
+    if fit not in VIEW_FITS:
+        raise ValueError(f"fit must be one of {VIEW_FITS}, got {fit!r}")
+    if isinstance(rotate, bool) or rotate not in (0, 90, 180, 270):
+        raise ValueError(f"rotate must be 0, 90, 180 or 270, got {rotate!r}")
+    if roi is None:
+        roi = (0.0, 0.0, float(ws), float(hs))
+    try:
+        x0, y0, x1, y1 = (float(v) for v in roi)
+    except (TypeError, ValueError):
+        raise ValueError(f"roi must be (x0, y0, x1, y1), got {roi!r}") from None
+    if not (np.isfinite([x0, y0, x1, y1]).all() and x1 > x0 and y1 > y0):
+        raise ValueError(f"empty roi {roi!r}: needs x1 > x0 and y1 > y0")
+    rw, rh = x1 - x0, y1 - y0
+    vw, vh = (rh, rw) if rotate in (90, 270) else (rw, rh)
+    if fit == "crop":
+        if hd != wd:
+            raise ValueError(f"fit='crop' needs a square view, got {hd}x{wd}")
+        short = hd * 8 // 7  # center_crop_plan: shorter side -> short, the other in proportion
+        sx, sy = (short * vw / vh, float(short)) if vh <= vw else (float(short), short * vh / vw)
+        sx, sy = float(int(sx)), float(int(sy))
+    else:
+        sx = sy = min(hd / vh, wd / vw)
+    cx0, kx = _fit_axis(fit, wd, vw, sx)
+    cy0, ky = _fit_axis(fit, hd, vh, sy)
+    gx = (np.arange(wd // VIEW_CELL + 1, dtype=np.float64) * VIEW_CELL - cx0) * kx
+    gy = (np.arange(hd // VIEW_CELL + 1, dtype=np.float64) * VIEW_CELL - cy0) * ky
+    xv, yv = np.meshgrid(gx, gy)  # view coordinates of every node
+    if mirror:
+        xv = vw - xv
+    if rotate == 90:
+        xv, yv = rw - yv, xv
+    elif rotate == 180:
+        xv, yv = rw - xv, rh - yv
+    elif rotate == 270:
+        xv, yv = yv, rh - xv
+    x, y = x0 + xv, y0 + yv
+    if homography is not None:
+        try:
+            h = np.asarray(homography, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("homography must be 3 x 3 numbers") from None
+        if h.shape != (3, 3) or not np.isfinite(h).all():
+            raise ValueError(f"homography must be 3 x 3 finite numbers, got shape {h.shape}")
+        if abs(np.linalg.det(h)) <= 1e-12 * max(1.0, np.abs(h).max()) ** 3:
+            raise ValueError("singular homography")
+        w = h[2, 0] * x + h[2, 1] * y + h[2, 2]
+        if (w <= 0).any():
+            raise ValueError("homography sends part of the view behind the camera")
+        x, y = ((h[0, 0] * x + h[0, 1] * y + h[0, 2]) / w,
+                (h[1, 0] * x + h[1, 1] * y + h[1, 2]) / w)
+    if lens is not None:
+        x, y = _lens_points(x, y, lens, ws)
+    nodes = np.rint(np.stack([x, y], -1) * 64.0)
+    return np.clip(np.nan_to_num(nodes, nan=-VIEW_NODE_LIM), -VIEW_NODE_LIM,
+                   VIEW_NODE_LIM - 1).astype(np.int32)
+
+
+def view_mesh_from(src_hw, dst_hw, view, fit: str = "letterbox"):
+    """(mesh, pad) of one twin / JSON view entry: null (the plain ``fit``) or an object with
+    ``VIEW_KEYS``.  Raises ValueError on anything else."""
+    if view is None:
+        view = {}
+    if not isinstance(view, dict):
+        raise ValueError(f"a view is an object or null, got {type(view).__name__}")
+    unknown = sorted(set(view) - set(VIEW_KEYS))
+    if unknown:
+        raise ValueError(f"unknown view keys {unknown}; known: {VIEW_KEYS}")
+    pad = view.get("pad", None)
+    if pad is None:
+        pad = 0 if fit == "crop" else LETTERBOX_PAD
+    if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= 255:
+        raise ValueError(f"view pad {pad!r} outside 0..255")
+    mirror = view.get("mirror", False)
+    if not isinstance(mirror, bool):
+        raise ValueError(f"view mirror must be true or false, got {mirror!r}")
+    mesh = view_mesh(src_hw, dst_hw, roi=view.get("roi"), rotate=view.get("rotate", 0),
+                     mirror=mirror, homography=view.get("homography"), lens=view.get("lens"),
+                     fit=fit)
+    return mesh, pad
+
+
+class CameraViews:
+    """The views of ``streams`` cameras of ``src_hw`` = (Hs, Ws) pixels into ``dst_hw`` =
+    (Hd, Wd) model pixels (multiples of 16): ``mesh`` int32 [streams, Hd/16 + 1, Wd/16 + 1, 2]
+    (:func:`view_mesh`) and ``pad`` int32 [streams], the tensors csrc/kernels/frame_warp.hip
+    reads every step -- so :meth:`set` takes effect from the next step without recapturing.
+    Every camera starts with the plain ``fit`` view."""
+
+    def __init__(self, streams: int, src_hw, dst_hw, device="cpu", fit: str = "letterbox"):
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        self.src_hw, self.dst_hw = _check_view_hw(src_hw, dst_hw)
+        self.streams, self.fit = int(streams), fit
+        plain, pad = view_mesh_from(self.src_hw, self.dst_hw, None, fit)
+        self.mesh = torch.from_numpy(plain).repeat(self.streams, 1, 1, 1).to(device)
+        self.pad = torch.full((self.streams,), pad, dtype=torch.int32, device=device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.mesh.device
+
+    def set(self, stream: int, mesh, pad: int = LETTERBOX_PAD) -> "CameraViews":
+        """Give camera ``stream`` the view ``mesh`` ([Hd/16 + 1, Wd/16 + 1, 2] integers; every
+        node value is clamped to [-2^20, 2^20), so no word in device memory can overflow the
+        kernel's arithmetic) and the padding grey ``pad``."""
+        if isinstance(stream, bool) or not 0 <= int(stream) < self.streams:
+            raise ValueError(f"camera {stream} outside 0..{self.streams - 1}")
+        if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= 255:
+            raise ValueError(f"pad {pad!r} outside 0..255")
+        m = torch.as_tensor(mesh)
+        if m.is_floating_point() or m.dtype == torch.bool or tuple(m.shape) != tuple(
+                self.mesh.shape[1:]):
+            raise ValueError(f"a view mesh is integer {list(self.mesh.shape[1:])}, got {m.dtype} "
+                             f"{list(m.shape)}")
+        m = m.to(torch.int64).clamp(-VIEW_NODE_LIM, VIEW_NODE_LIM - 1).to(torch.int32)
+        self.mesh[int(stream)].copy_(m)
+        self.pad[int(stream)] = pad
+        return self
+
+    def set_view(self, stream: int, view) -> "CameraViews":
+        """:meth:`set` from a twin / JSON entry (:func:`view_mesh_from`)."""
+        return self.set(stream, *view_mesh_from(self.src_hw, self.dst_hw, view, self.fit))
+
+
+@dataclass(frozen=True)
+class ViewSlots:
+    """Batch rows of a slice as cameras ``slot0 ..`` of ``views``: what the engine hands the
+    models in place of a ResizePlan, so that :func:`det_to_source` maps their boxes through
+    the mesh (:func:`view_to_source`)."""
+    views: CameraViews
+    slot0: int = 0
+
+    @property
+    def src_hw(self):
+        return self.views.src_hw
+
+    @property
+    def dst_hw(self):
+        return self.views.dst_hw
+
+
+def _check_views(views, n: int, slot0: int, device) -> int:
+    if not isinstance(views, CameraViews):
+        raise TypeError(f"views must be an ops.CameraViews, got {type(views).__name__}")
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > views.streams:
+        raise ValueError(f"cameras [{slot0}, {slot0 + n}) outside the views' {views.streams}")
+    if views.device != device:
+        raise ValueError(f"frames on {device}, views on {views.device}")
+    return slot0
+
+
+def frame_warp(src: torch.Tensor, views: CameraViews, out: Optional[torch.Tensor] = None,
+               slot0: int = 0, src_format: str = "rgb") -> torch.Tensor:
+    """uint8 frames [N, Hs, Ws, 3] -> [N, Hd, Wd, 3], batch row n through the view of camera
+    ``slot0 + n`` of ``views``: a bilinear mesh gives every destination pixel a source position
+    in 2^-16 pixel, sampled with :func:`frame_resize`'s 11-bit bilinear; positions outside the
+    frame are the camera's ``pad``; every byte of ``out`` is written.  The rule is written out
+    in ops.reference.frame_warp; GPU (csrc/kernels/frame_warp.hip) and CPU are bit-identical.
+    ``src_format="nv12"``: ``src`` is NV12 [N, Hs * 3 // 2, Ws] and the result equals
+    ``frame_warp(nv12_to_rgb(src), ...)`` byte for byte."""
+    _check_format(src_format)
+    nv12 = src_format == "nv12"
+    if not isinstance(views, CameraViews):
+        raise TypeError(f"views must be an ops.CameraViews, got {type(views).__name__}")
+    if nv12:
+        hw = _check_nv12(src, views.src_hw[0])
+    else:
+        if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+            raise ValueError(f"RGB frames are uint8 [N, Hs, Ws, 3], got {src.dtype} "
+                             f"{tuple(src.shape)}")
+        hw = (int(src.shape[1]), int(src.shape[2]))
+    if hw != views.src_hw:
+        raise ValueError(f"frames of {hw[0]}x{hw[1]}, the views were made for "
+                         f"{views.src_hw[0]}x{views.src_hw[1]}")
+    n = int(src.shape[0])
+    slot0 = _check_views(views, n, slot0, src.device)
+    if out is None:
+        out = torch.empty(n, *views.dst_hw, 3, dtype=torch.uint8, device=src.device)
+    if tuple(out.shape) != (n, *views.dst_hw, 3) or out.dtype != torch.uint8:
+        raise ValueError(f"out must be uint8 {[n, *views.dst_hw, 3]}, got {out.dtype} "
+                         f"{list(out.shape)}")
+    if src.is_cuda:
+        _native().frame_warp(src, out, views.mesh, views.pad, slot0, nv12)
+    else:
+        _ref.frame_warp(_ref.nv12_to_rgb(src) if nv12 else src, views.mesh[slot0:slot0 + n],
+                        views.pad[slot0:slot0 + n], out)
+    return out
+
+
+def view_to_source(det: torch.Tensor, count: torch.Tensor, views: CameraViews,
+                   slot0: int = 0) -> torch.Tensor:
+    """Kept boxes of :func:`nms` (det fp32 [N, max_det, 6], rows < count[n]) from the view
+    pixels of camera ``slot0 + n`` to source-frame pixels, in place.  Each edge is quantised to
+    quarter view pixels with the tracker's rule (NaN -> 0; at most 4096 pixels) and clamped to
+    the view; the four corners and the four edge midpoints go through the mesh and the row
+    becomes their axis-aligned hull, clamped to the frame.  Exact for roi, rotation and mirror
+    views; for lens and perspective views it is the hull of those eight samples, which a
+    strongly curved edge can leave by a fraction of its sag.  Score, class and the rows past
+    count are untouched.  GPU and CPU (ops.reference.view_to_source) are bit-identical."""
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6:
+        raise ValueError(f"det must be fp32 [N, max_det, 6], got {det.dtype} {tuple(det.shape)}")
+    n = int(det.shape[0])
+    slot0 = _check_views(views, n, slot0, det.device)
+    if det.is_cuda:
+        _native().view_to_source(det, count, views.mesh, *views.src_hw, *views.dst_hw, slot0)
+    else:
+        _ref.view_to_source(det, count, views.mesh[slot0:slot0 + n], views.dst_hw, views.src_hw)
     return det
 
 

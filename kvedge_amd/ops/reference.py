@@ -284,6 +284,82 @@ def track_class(c):
     return v.clamp(0.0, 65535.0).to(torch.int64)
 
 
+def _warp_tap(P, S):
+    """Position P (2^-16 pixel, pixel-corner coordinates, inside [0, S << 16)) -> the two
+    source taps and the 11-bit weight of the second one (csrc/kernels/frame_warp.hip)."""
+    Pc = P - 32768
+    q = Pc >> 16
+    w = ((Pc & 0xffff) + 16) >> 5
+    w = np.where((q < 0) | (q >= S - 1), 0, w)
+    q = np.clip(q, 0, S - 1)
+    return q, np.minimum(q + 1, S - 1), w
+
+
+def frame_warp(src, mesh, pad, out):
+    """Mesh-driven warp of uint8 frames [N, Hs, Ws, 3] into out [N, Hd, Wd, 3], Hd and Wd
+    multiples of 16.  mesh int32 [N, Hd/16 + 1, Wd/16 + 1, 2]: node (gy, gx) is the source
+    position (x, y), in 1/64 pixel and pixel-corner coordinates, that destination corner
+    point (16 gx, 16 gy) samples; pad int32 [N].  Destination pixel (dx, dy): cell (dx >> 4,
+    dy >> 4), odd weights u = 2 (dx & 15) + 1, v likewise (the pixel centre in 1/32 cell),
+    P = n00 (32-u)(32-v) + n01 u (32-v) + n10 (32-u) v + n11 u v in 2^-16 pixel; outside
+    [0, S << 16) on either axis the pixel is pad[n]; else taps and weights by ``_warp_tap`` and
+    frame_resize's blend.  THE definition csrc/kernels/frame_warp.hip equals byte for byte."""
+    N, Hs, Ws, _ = src.shape
+    Hd, Wd = out.shape[1:3]
+    m = mesh.numpy().astype(np.int64)
+    dy, dx = np.arange(Hd), np.arange(Wd)
+    cy, cx = (dy >> 4)[:, None], (dx >> 4)[None, :]
+    v = (2 * (dy & 15) + 1)[None, :, None, None]
+    u = (2 * (dx & 15) + 1)[None, None, :, None]
+    P = (m[:, cy, cx] * ((32 - u) * (32 - v)) + m[:, cy, cx + 1] * (u * (32 - v)) +
+         m[:, cy + 1, cx] * ((32 - u) * v) + m[:, cy + 1, cx + 1] * (u * v))  # [N, Hd, Wd, 2]
+    X, Y = P[..., 0], P[..., 1]
+    outside = (X < 0) | (X >= Ws << 16) | (Y < 0) | (Y >= Hs << 16)
+    x0, x1, wx = _warp_tap(X, Ws)
+    y0, y1, wy = _warp_tap(Y, Hs)
+    s = src.numpy()
+    n = np.arange(N)[:, None, None]
+    wx, wy = wx[..., None], wy[..., None]
+    top = s[n, y0, x0].astype(np.int64) * (2048 - wx) + s[n, y0, x1].astype(np.int64) * wx
+    bot = s[n, y1, x0].astype(np.int64) * (2048 - wx) + s[n, y1, x1].astype(np.int64) * wx
+    y = (top * (2048 - wy) + bot * wy + (1 << 21)) >> 22
+    fill = (pad.numpy().astype(np.int64) & 255)[:, None, None, None]
+    out.copy_(torch.from_numpy(np.where(outside[..., None], fill, y).astype(np.uint8)))
+    return out
+
+
+def view_to_source(det, count, mesh, dst_hw, src_hw):
+    """Kept boxes (rows < count[n] of det fp32 [N, max_det, 6]) from view pixels to
+    source-frame pixels through mesh int32 [N, Hd/16 + 1, Wd/16 + 1, 2], in place.  Each edge
+    is quantised to quarter pixels (``track_quantize``) and clamped to the view; the four
+    corners and the four edge midpoints ((a + b) >> 1) go through the mesh -- cell p >> 6
+    clamped to the last one, weights u = p - 64 cell in 0..64, X = sum of node * weights (sum
+    4096), Xq = (X + 2048) >> 12 in 1/64 source pixel -- and the row becomes their axis-aligned
+    hull, Xq / 64 clamped to the frame.  THE definition the kernel equals bit for bit."""
+    N, max_det, _ = det.shape
+    (Hd, Wd), (Hs, Ws) = dst_hw, src_hw
+    q = track_quantize(det[..., :4]).numpy()
+    x1, x2 = np.minimum(q[..., 0], 4 * Wd), np.minimum(q[..., 2], 4 * Wd)
+    y1, y2 = np.minimum(q[..., 1], 4 * Hd), np.minimum(q[..., 3], 4 * Hd)
+    xm, ym = (x1 + x2) >> 1, (y1 + y2) >> 1
+    px = np.stack([x1, x2, x1, x2, xm, xm, x1, x2], -1)  # [N, max_det, 8]
+    py = np.stack([y1, y1, y2, y2, y1, y2, ym, ym], -1)
+    cx, cy = np.minimum(px >> 6, Wd // 16 - 1), np.minimum(py >> 6, Hd // 16 - 1)
+    u, v = (px - 64 * cx)[..., None], (py - 64 * cy)[..., None]
+    m = mesh.numpy().astype(np.int64)
+    n = np.arange(N)[:, None, None]
+    P = (m[n, cy, cx] * ((64 - u) * (64 - v)) + m[n, cy, cx + 1] * (u * (64 - v)) +
+         m[n, cy + 1, cx] * ((64 - u) * v) + m[n, cy + 1, cx + 1] * (u * v))
+    Pq = (P + 2048) >> 12  # [N, max_det, 8, 2]
+    lo, hi = Pq.min(2), Pq.max(2)
+    lim = np.array([Ws, Hs, Ws, Hs], dtype=np.float32)
+    hull = np.concatenate([lo, hi], -1).astype(np.float32) / np.float32(64.0)
+    new = torch.from_numpy(np.minimum(np.maximum(hull, np.float32(0.0)), lim))
+    live = (torch.arange(max_det).view(1, max_det) < count.view(N, 1).long()).unsqueeze(-1)
+    det[..., :4] = torch.where(live, new, det[..., :4])
+    return det
+
+
 def _box_area(b):
     return (b[..., 2] - b[..., 0]).clamp_min(0) * (b[..., 3] - b[..., 1]).clamp_min(0)
 
