@@ -1021,6 +1021,56 @@ void frame_watch(const at::Tensor& src, at::Tensor& state, at::Tensor& stats, at
   TORCH_CHECK(rc == 0, "kvedge: frame_watch failed rc=", rc);
 }
 
+// K26: low-light enhancement (csrc/kernels/frame_enhance.hip).  images / dst uint8 RGB
+// [N,H,W,3] (the same tensor: in place); params, axis, luts and sums are an ops.FrameEnhance's
+// tensors, batch row n is camera slot0 + n.  Everything is validated before the first launch.
+void frame_enhance(const at::Tensor& images, at::Tensor& dst, const at::Tensor& params,
+                   const at::Tensor& axis, at::Tensor& luts, at::Tensor& sums, at::Tensor& stats,
+                   int64_t slot0, int64_t TY, int64_t TX, int64_t hist_copies) {
+  check_dev(images, "images");
+  check_dev(dst, "dst");
+  check_dev(params, "params");
+  check_dev(axis, "axis");
+  check_dev(luts, "luts");
+  check_dev(sums, "sums");
+  check_dev(stats, "stats");
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3,
+              "kvedge: frame_enhance images uint8 [N,H,W,3]");
+  const int64_t N = images.size(0), H = images.size(1), W = images.size(2);
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
+              "kvedge: frame_enhance frame size 1..4096 on each axis, got ", H, "x", W);
+  TORCH_CHECK(dst.scalar_type() == at::kByte && dst.sizes() == images.sizes(),
+              "kvedge: frame_enhance dst uint8 [N,H,W,3] like images");
+  TORCH_CHECK(TY >= 1 && TY <= 16 && TX >= 1 && TX <= 16, "kvedge: frame_enhance tiles 1..16");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 8,
+              "kvedge: frame_enhance params int32 [S,8]");
+  const int64_t S = params.size(0), T = TY * TX;
+  TORCH_CHECK(axis.scalar_type() == at::kInt && axis.dim() == 1 &&
+                  axis.size(0) == W + H + TY + 2,
+              "kvedge: frame_enhance axis int32 [W+H+TY+2] for the frame size and grid");
+  TORCH_CHECK(luts.scalar_type() == at::kByte && luts.dim() == 3 && luts.size(0) == S &&
+                  luts.size(1) == T && luts.size(2) == 256,
+              "kvedge: frame_enhance luts uint8 [S,TY*TX,256]");
+  TORCH_CHECK(sums.scalar_type() == at::kInt && sums.dim() == 2 && sums.size(0) == S &&
+                  sums.size(1) == T, "kvedge: frame_enhance sums int32 [S,TY*TX]");
+  TORCH_CHECK(stats.scalar_type() == at::kInt && stats.dim() == 2 && stats.size(0) == N &&
+                  stats.size(1) == 2, "kvedge: frame_enhance stats int32 [N,2]");
+  TORCH_CHECK(S < (1ll << 24) && N <= 65535, "kvedge: frame_enhance too many cameras");
+  TORCH_CHECK(slot0 >= 0 && slot0 + N <= S, "kvedge: frame_enhance cameras [", slot0, ", ",
+              slot0 + N, ") outside the enhancer's ", S);
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&dst, &params, &axis, &luts,
+                                                                      &sums, &stats})
+    TORCH_CHECK(t->device() == images.device(),
+                "kvedge: frame_enhance operands on different devices");
+  const c10::DeviceGuard g(images.device());
+  const int rc = kv_frame_enhance(images.data_ptr<uint8_t>(), dst.data_ptr<uint8_t>(),
+                                  params.data_ptr<int>(), axis.data_ptr<int>(),
+                                  luts.data_ptr<uint8_t>(), sums.data_ptr<int>(),
+                                  stats.data_ptr<int>(), (int)N, (int)S, (int)slot0, (int)H,
+                                  (int)W, (int)TY, (int)TX, (int)hist_copies, cur_stream(images));
+  TORCH_CHECK(rc == 0, "kvedge: frame_enhance failed rc=", rc);
+}
+
 // K21: baseline JPEG encoder (csrc/kernels/jpeg_encode.hip).  images uint8 [M,H,W,3]; the
 // tables, the header and the workspaces belong to an ops.JpegEncoder made for (H, W) and the
 // subsampling; out uint8 [rows >= M, cap], length int32 [rows].  Everything is validated before
@@ -1330,6 +1380,8 @@ TORCH_LIBRARY(kvedge, m) {
         "Tensor table, Tensor(b!) zone_mask, Tensor(c!) zone_counts, int slot0) -> ()");
   m.def("frame_watch(Tensor src, Tensor(a!) state, Tensor(b!) stats, Tensor(c!) mask, int slot0, "
         "bool nv12, int cell, int row_step, int bg_shift) -> ()");
+  m.def("frame_enhance(Tensor images, Tensor(a!) dst, Tensor params, Tensor axis, Tensor(b!) luts, "
+        "Tensor(c!) sums, Tensor(d!) stats, int slot0, int TY, int TX, int hist_copies) -> ()");
   m.def("jpeg_encode(Tensor images, Tensor qtab, Tensor huff, Tensor header, Tensor(a!) coef, "
         "Tensor(b!) scratch, Tensor(c!) seglen, Tensor(d!) out, Tensor(e!) length, bool sub420) "
         "-> ()");
@@ -1386,6 +1438,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("track_update", track_update);
   m.impl("zone_update", zone_update);
   m.impl("frame_watch", frame_watch);
+  m.impl("frame_enhance", frame_enhance);
   m.impl("jpeg_encode", jpeg_encode);
   m.impl("annotate", annotate);
   m.impl("motion_blobs", motion_blobs);

@@ -254,6 +254,20 @@ int kv_watch_state_stride(int cells);
 int kv_frame_watch(const unsigned char* src, int* state, int* stats, unsigned char* mask, int N,
                    int S, int slot0, int Hs, int Ws, int nv12, int cell, int row_step,
                    int bg_shift, hipStream_t s);
+// K26 (frame_enhance.hip): low-light enhancement (CLAHE on luma, chroma kept) of images uint8
+// RGB [N,H,W,3] into dst (dst == src: in place), batch row n = camera slot0 + n, two launches.
+// params int32 [S,8] (mode, strength, clip_q8, lo16, hi16; clamped in the kernel), axis int32
+// [W + H + TY + 2] (per column and per row cell | w << 8, then the row bands' first rows), luts
+// uint8 [S, TY TX, 256] and sums int32 [S, TY TX] (workspace between the launches) belong to an
+// ops.FrameEnhance; stats int32 [N,2] = mean16, alpha, every element written.  hist_copies:
+// LDS histogram copies per wave in the table launch.  Byte-identical to
+// ops.reference.frame_enhance; the rules and the layout are at the top of frame_enhance.hip.
+// Returns -1 H or W outside 1..4096, -2 slot0 + N > S, -3 TY or TX outside 1..16, -4 a grid that
+// leaves a tile empty, -5 hist_copies not 1/2/4/8, -7 misaligned params, luts, sums or stats,
+// -8 axis not 16-byte aligned, -9 N too large.  N == 0 launches nothing.
+int kv_frame_enhance(const unsigned char* src, unsigned char* dst, const int* params,
+                     const int* axis, unsigned char* luts, int* sums, int* stats, int N, int S,
+                     int slot0, int H, int W, int TY, int TX, int hist_copies, hipStream_t s);
 // K21 (jpeg_encode.hip): baseline JPEG files of images uint8 RGB [M,H,W,3], three launches.
 // qtab int32 [2,64] (luminance, chrominance quantisers in natural order, clamped to 1..255),
 // huff int32 [4,256] (code | length << 16 by symbol: DC lum, DC chroma, AC lum, AC chroma) and

@@ -85,6 +85,15 @@ class InferenceEngine:
     back to frame pixels through the same meshes (ops.view_to_source), so everything after the
     model still sees native-frame pixels.  The meshes live in device memory outside the graph:
     ``views.set`` changes a camera's view from the next step, no recapture.  Needs ``frame_hw``.
+    enhance: an ops.FrameEnhance with one camera per batch row at model size: every step runs
+    ops.frame_enhance (CLAHE on luma for dark cameras) on the model-size frames, after the
+    resize / warp and before the model, in place; its per-camera words live in device memory
+    outside the graph (``enhance.set_mode`` ... take effect from the next step, no recapture) and
+    the per-camera (mean16, alpha) of the last step are in ``enhance_stats`` [batch, 2].  Without
+    ``frame_hw`` the model-size buffer is the fed input, which need not be refreshed every step:
+    the frames are then enhanced into a second buffer and the model reads that one.  A frame
+    watch served at native resolution still sees the untouched source frames; served at model
+    size it sees what the model sees, the enhanced frames.
     A model with ``stateful = True`` (models.tracking.KvTracked) keeps device state across steps,
     one entry per batch row: it is called with ``slot0`` = the first batch row of the slice, its
     state is left freshly reset by ``prepare()`` (``reset_tracks()`` does the same later), and
@@ -94,7 +103,8 @@ class InferenceEngine:
     def __init__(self, model: Callable, batch: int, image_size: int, device="cuda",
                  seed: int = 0, use_graph: bool = True, synthetic: bool = True,
                  streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None,
-                 frame_format: str = "rgb", views: Optional["ops.CameraViews"] = None):
+                 frame_format: str = "rgb", views: Optional["ops.CameraViews"] = None,
+                 enhance: Optional["ops.FrameEnhance"] = None):
         if frame_format not in ops.SRC_FORMATS:
             raise ValueError(f"frame_format must be one of {ops.SRC_FORMATS}, "
                              f"got {frame_format!r}")
@@ -141,6 +151,20 @@ class InferenceEngine:
             if want != have:
                 raise ValueError(f"views are (cameras, frame, model size, device) = {have}, the "
                                  f"engine needs {want}")
+        self.enhance = enhance
+        self.enhance_stats = self.enhanced = None
+        if enhance is not None:
+            if not isinstance(enhance, ops.FrameEnhance):
+                raise TypeError("enhance must be an ops.FrameEnhance, got "
+                                f"{type(enhance).__name__}")
+            want = (batch, (image_size, image_size), self.device.type)
+            have = (enhance.streams, enhance.hw, enhance.device.type)
+            if want != have:
+                raise ValueError(f"enhance is (cameras, model size, device) = {have}, the "
+                                 f"engine needs {want}")
+            self.enhance_stats = torch.zeros(batch, 2, dtype=torch.int32, device=self.device)
+            if self.frame_hw is None:  # the fed input stays as it was fed
+                self.enhanced = torch.empty_like(self.frames)
         # [step counter, finished-block count]: synth_frames bumps it in-kernel (one launch)
         self.step_ctr = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.outputs = None
@@ -188,6 +212,8 @@ class InferenceEngine:
             # the models hand ``plan`` to ops.det_to_source, which maps through the meshes
             ops.frame_warp(self.source_frames[lo:hi], self.views, out=frames, slot0=lo, **fmt)
             plan = ops.ViewSlots(self.views, lo)
+        if self.enhance is not None:
+            ops.frame_enhance(frames, self.enhance, slot0=lo, out_stats=self.enhance_stats[lo:hi])
         if hasattr(self.model, "from_source"):
             return self.model.from_source(self.source_frames[lo:hi], frames, plan,
                                           **self._slot(lo), **fmt)
@@ -195,6 +221,15 @@ class InferenceEngine:
         if hasattr(self.model, "to_source"):
             out = self.model.to_source(out, plan)
         return out
+
+    def _run_fed(self, lo: int, hi: int):
+        """Images [lo, hi) of model-size input on the current stream: (enhance ->) model."""
+        frames = self.frames[lo:hi]
+        if self.enhance is not None:
+            frames, _ = ops.frame_enhance(frames, self.enhance, slot0=lo,
+                                          out=self.enhanced[lo:hi],
+                                          out_stats=self.enhance_stats[lo:hi])
+        return self.model(frames, **self._slot(lo))
 
     def _slot(self, lo: int) -> dict:
         """A stateful model (models.tracking.KvTracked: batch row n is camera n) is told which
@@ -212,7 +247,7 @@ class InferenceEngine:
 
     def _forward(self):
         if not self._side:
-            self.outputs = (self.model(self.frames, **self._slot(0)) if self.frame_plan is None
+            self.outputs = (self._run_fed(0, self.batch) if self.frame_plan is None
                             else self._run_slice(0, self.batch))
             return self.outputs
         cur = torch.cuda.current_stream(self.device)
@@ -221,8 +256,7 @@ class InferenceEngine:
         for i, s in enumerate(self._side):
             s.wait_stream(cur)
             with torch.cuda.stream(s):
-                parts.append(self.model(self.frames[i * per:(i + 1) * per],
-                                        **self._slot(i * per))
+                parts.append(self._run_fed(i * per, (i + 1) * per)
                              if self.frame_plan is None
                              else self._run_slice(i * per, (i + 1) * per))
         for s in self._side:

@@ -176,6 +176,10 @@ def main(argv=None):
     ap.add_argument("--privacy-zones-json", default="",
                     help="polygons hidden under a mosaic, inline JSON '[{\"name\": ..., "
                          "\"polygon\": [[x, y], ...], \"cameras\"?}]' (at most 8, 3..8 vertices)")
+    ap.add_argument("--enhance", default="", choices=["on", "auto"],
+                    help="low-light enhancement (CLAHE on luma) of the model-size frames on the "
+                         "device: `on` for every camera, `auto` for dark ones (twin keys "
+                         "`enhance`, `enhance_mode`; telemetry gains `enhanced`)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -235,7 +239,9 @@ def main(argv=None):
                        snapshot_annotate=a.snapshot_annotate,
                        snapshot_labels=a.snapshot_labels,
                        snapshot_privacy_classes=a.privacy_classes,
-                       snapshot_privacy_zones=a.privacy_zones_json).validate()
+                       snapshot_privacy_zones=a.privacy_zones_json,
+                       enhance=bool(a.enhance),
+                       enhance_mode=a.enhance or d.enhance_mode).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub
     kind = a.transport if di.local_rank == 0 or a.transport != "azure" else "null"
     try:

@@ -203,6 +203,7 @@ class ModuleApp:
         self.camera_totals = None  # module.watch.CameraTotals with `watch` on
         self.snapshots = None  # module.snapshots.SnapshotSender with `snapshots` on
         self.views = None  # ops.CameraViews with `views` configured
+        self.enhance = None  # ops.FrameEnhance with `enhance` on
         self.ring = None
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
@@ -407,6 +408,7 @@ class ModuleApp:
         self.camera_totals = None
         self.snapshots = None
         self.views = None
+        self.enhance = None
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -481,6 +483,11 @@ class ModuleApp:
             self.views = ops.CameraViews(cfg.batch, cfg.frame_hw(), (size, size), dev,
                                          fit=cfg.view_fit())
             self._apply_views(cfg)
+        self.enhance = None
+        if cfg.enhance:  # per-camera words in device memory: live keys need no rebuild
+            size = cfg.resolved_image_size()
+            self.enhance = ops.FrameEnhance(cfg.batch, (size, size), device=dev)
+            self._apply_enhance(cfg)
         camera = cfg.is_camera()
         t_model = time.time()
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
@@ -488,7 +495,7 @@ class ModuleApp:
                                       synthetic=not camera,
                                       streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1,
                                       frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format(),
-                                      views=self.views)
+                                      views=self.views, enhance=self.enhance)
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
@@ -543,7 +550,7 @@ class ModuleApp:
         err = next((e for e in errs if e), None)
         if err is not None:
             self.engine = self.model = self.zone_totals = self.camera_totals = None
-            self.sim = self.snapshots = self.views = None
+            self.sim = self.snapshots = self.views = self.enhance = None
             self._stop_camera()
             if previous is None:
                 return err
@@ -783,6 +790,9 @@ class ModuleApp:
             if g:
                 msg["gpu"] = g
         msg.update(self._outputs_summary())
+        if self.enhance is not None and self.engine is not None:
+            # cameras the last step enhanced (alpha > 0)
+            msg["enhanced"] = int((self.engine.enhance_stats[:, 1] > 0).sum())
         if self.snapshots is not None:
             msg["snapshots"] = self.snapshots.summary()
         if self.rank == 0:
@@ -859,6 +869,12 @@ class ModuleApp:
             else:
                 self.views.set_view(cam, None)
 
+    def _apply_enhance(self, cfg: ModuleConfig) -> None:
+        """The ``enhance_*`` keys into the device words of every camera."""
+        e = self.enhance
+        e.set_mode(cfg.enhance_mode).set_strength(ops.enhance_strength_q(cfg.enhance_strength))
+        e.set_clip(cfg.enhance_clip).set_levels(cfg.enhance_dark_level, cfg.enhance_bright_level)
+
     def _apply_patch(self, patch: Dict[str, Any]) -> Tuple[int, Dict[str, Any]]:
         try:
             new = self.cfg.apply_patch(patch)
@@ -884,6 +900,11 @@ class ModuleApp:
                 and self.cfg.views != old.views):
             # the view meshes too: the next replay warps through the new ones
             self._apply_views(self.cfg)
+        if (self.enhance is not None and not self.cfg.needs_rebuild(old)
+                and any(getattr(self.cfg, k) != getattr(old, k)
+                        for k in ModuleConfig.ENHANCE_LIVE_KEYS)):
+            # the enhancement words too: the next replay reads the new ones
+            self._apply_enhance(self.cfg)
         if (self.snapshots is not None and not self.cfg.needs_rebuild(old)
                 and self.cfg.snapshot_quality != old.snapshot_quality):
             # the quantisation tables live in device memory, like the watch thresholds

@@ -16,6 +16,7 @@ MODELS = ("resnet50", "yolov8n", "detect-classify", "simulated-temperature")
 SOURCES = ("synthetic", "camera", "camera-nv12")
 DTYPES = ("bf16",)
 ZONE_ANCHORS = ("bottom", "centre")
+ENHANCE_MODES = ("on", "auto")  # `enhance` false is off
 MAX_REGIONS = 8  # lines, and zones, per camera (csrc/kernels/zones.hip)
 SNAPSHOT_SUBSAMPLINGS = ("420", "444")
 SNAPSHOT_LABELS = ("none", "class", "id", "both")
@@ -239,6 +240,18 @@ class ModuleConfig:
     snapshot_privacy_classes: Tuple[int, ...] = ()
     snapshot_privacy_block: int = 8
     snapshot_privacy_zones: Tuple[Dict[str, Any], ...] = ()
+    # low-light enhancement (ops.frame_enhance): CLAHE on the luma of the model-size frames
+    # before the model, chroma kept.  enhance_mode "on" blends every camera at
+    # enhance_strength (0..1); "auto" scales that by how dark the camera is: in full at a mean
+    # luma of enhance_dark_level or below, not at all from enhance_bright_level up.
+    # enhance_clip (1..64) is the clip limit in multiples of a flat histogram's bin.  Only
+    # `enhance` needs a rebuild: the others are words the device reads at every step
+    enhance: bool = False
+    enhance_mode: str = "auto"
+    enhance_strength: float = 1.0
+    enhance_clip: float = 2.0
+    enhance_dark_level: float = 24.0
+    enhance_bright_level: float = 64.0
     native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -262,7 +275,7 @@ class ModuleConfig:
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
                "watch_bg_shift", "watch_regions", "watch_region_max",
                "watch_region_connectivity", "snapshots", "snapshot_width", "snapshot_subsampling",
-               "snapshot_annotate")
+               "snapshot_annotate", "enhance")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
@@ -444,6 +457,20 @@ class ModuleConfig:
                     if getattr(self, k) != base[k].default:
                         raise ValueError(f"{k} needs a detector: model {self.model} has no "
                                          f"boxes (snapshot_privacy_zones work with any model)")
+        # the ranges of ops.FrameEnhance's setters
+        if self.enhance_mode not in ENHANCE_MODES:
+            raise ValueError(f"enhance_mode must be one of {ENHANCE_MODES}, "
+                             f"got {self.enhance_mode!r}")
+        if not 0.0 <= self.enhance_strength <= 1.0:
+            raise ValueError("enhance_strength must be in [0, 1]")
+        if not 1.0 <= self.enhance_clip <= 64.0:
+            raise ValueError("enhance_clip must be 1..64")
+        if not (0.0 <= self.enhance_dark_level <= 255.0
+                and self.enhance_dark_level + 1.0 <= self.enhance_bright_level <= 256.0):
+            raise ValueError("enhance_dark_level must be 0..255 and enhance_bright_level at "
+                             "least one level above it, at most 256")
+        if self.enhance and self.model == "simulated-temperature":
+            raise ValueError("enhance needs frames: a vision model")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -531,6 +558,10 @@ class ModuleConfig:
                    "watch_region_min_cells", "watch_ignore")
     REGION_LIVE_KEYS = ("watch_region_min_cells", "watch_ignore")
 
+    ENHANCE_LIVE_KEYS = ("enhance_mode", "enhance_strength", "enhance_clip",
+                         "enhance_dark_level", "enhance_bright_level")
+    ENHANCE_KEYS = ("enhance",) + ENHANCE_LIVE_KEYS
+
     SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
                      "snapshot_every_s", "snapshot_max_bytes")
 
@@ -595,4 +626,8 @@ class ModuleConfig:
         else:
             d["snapshot_privacy_classes"] = list(d["snapshot_privacy_classes"])
             d["snapshot_privacy_zones"] = list(d["snapshot_privacy_zones"])
+        # and the enhancement keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.ENHANCE_KEYS):
+            for k in self.ENHANCE_KEYS:
+                d.pop(k)
         return d

@@ -1726,6 +1726,169 @@ def frame_watch(src: torch.Tensor, state: WatchState, slot0: int = 0, src_format
 
 
 # ---------------------------------------------------------------------------
+# low-light enhancement: per-camera CLAHE on luma (csrc/kernels/frame_enhance.hip)
+# ---------------------------------------------------------------------------
+ENHANCE_MODES = _ref.ENHANCE_MODES
+ENHANCE_PARAMS = _ref.ENHANCE_PARAMS
+ENHANCE_PARAM_RANGES = _ref.ENHANCE_PARAM_RANGES
+ENHANCE_MAX_TILES = _ref.ENHANCE_MAX_TILES
+ENHANCE_MAX_EXTENT = _ref.ENHANCE_MAX_EXTENT
+ENHANCE_STATS = ("mean16", "alpha")
+# on at full strength, clip limit 2.0; auto ramps in between mean luma 64 (off) and 24 (full),
+# the watch's default dark level
+ENHANCE_DEFAULTS = {"mode": 1, "strength": 256, "clip_q8": 512, "lo16": 384, "hi16": 1024}
+
+
+def enhance_strength_q(strength: float) -> int:
+    """A blend strength 0..1 in 1/256: floor(strength * 256 + 0.5)."""
+    import math
+
+    return int(math.floor(float(strength) * 256 + 0.5))
+
+
+class FrameEnhance:
+    """Low-light enhancement of ``streams`` cameras of ``hw`` = (H, W) pixel frames on a grid
+    of ``tiles`` = (TY, TX) tiles, and the device memory csrc/kernels/frame_enhance.hip works
+    in: ``params`` int32 [streams, 8] (``ENHANCE_PARAMS``, read and clamped every step, so the
+    setters take effect from the next step without recapturing), ``axis`` int32
+    [W + H + TY + 2] (per column and per row the table cell and the weight, ``cell | w << 8``,
+    then the first row of every row band), ``luts`` uint8 [streams, TY TX, 256] and ``sums``
+    int32 [streams, TY TX] (the per-tile tables and luma sums between the two launches)."""
+
+    def __init__(self, streams: int, hw, tiles=(8, 8), device="cpu"):
+        if streams < 1:
+            raise ValueError(f"streams must be >= 1, got {streams}")
+        h, w = int(hw[0]), int(hw[1])
+        if not (1 <= h <= ENHANCE_MAX_EXTENT and 1 <= w <= ENHANCE_MAX_EXTENT):
+            raise ValueError(f"frame_enhance frames are 1..{ENHANCE_MAX_EXTENT} pixels on each "
+                             f"axis, got {h}x{w}")
+        ty, tx = int(tiles[0]), int(tiles[1])
+        if not (1 <= ty <= ENHANCE_MAX_TILES and 1 <= tx <= ENHANCE_MAX_TILES):
+            raise ValueError(f"tiles are 1..{ENHANCE_MAX_TILES} on each axis, got {tiles}")
+        th, tw = -(-h // ty), -(-w // tx)
+        if (ty - 1) * th >= h or (tx - 1) * tw >= w:
+            raise ValueError(f"a {ty}x{tx} grid of {th}x{tw} tiles leaves a tile of a {h}x{w} "
+                             f"frame empty")
+        import numpy as np
+
+        self.streams, self.hw, self.tiles = int(streams), (h, w), (ty, tx)
+        # LDS histogram copies per wave in the table launch (1, 2, 4 or 8; docs/kernels.md)
+        self.hist_copies = 4
+        self.params = torch.zeros(self.streams, 8, dtype=torch.int32, device=device)
+        self.luts = torch.zeros(self.streams, ty * tx, 256, dtype=torch.uint8, device=device)
+        self.sums = torch.zeros(self.streams, ty * tx, dtype=torch.int32, device=device)
+        words = []
+        for size, t in ((w, tx), (h, ty)):
+            # cell k of an axis reads tiles (max(k - 1, 0), min(k, t - 1)): 0 before the first
+            # tile centre, t past the last one
+            s = -(-size // t)
+            a = 2 * np.arange(size) + 1 - s
+            cell = np.where(a <= 0, 0, np.minimum(a // (2 * s), t - 1) + 1)
+            words.append(cell | (_ref.enhance_axis(size, t)[2] << 8))
+        ycell = words[1] & 0xff
+        words.append(np.searchsorted(ycell, np.arange(ty + 2)))  # band b = rows of cell b
+        self.axis = torch.from_numpy(np.concatenate(words).astype(np.int32)).to(device)
+        for name, v in ENHANCE_DEFAULTS.items():
+            self._set(None, name, v)
+
+    @property
+    def device(self) -> torch.device:
+        return self.params.device
+
+    def _set(self, camera, name: str, v: int) -> "FrameEnhance":
+        i = ENHANCE_PARAMS.index(name)
+        lo, hi = ENHANCE_PARAM_RANGES[i]
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"enhance parameter {name} = {v!r} outside {lo}..{hi}")
+        if camera is None:
+            rows = slice(None)
+        elif not 0 <= int(camera) < self.streams:
+            raise ValueError(f"camera {camera} outside 0..{self.streams - 1}")
+        else:
+            rows = slice(int(camera), int(camera) + 1)
+        self.params[rows, i] = v
+        return self
+
+    def set_mode(self, mode, camera=None) -> "FrameEnhance":
+        """``mode``: "off", "on" (blend at ``strength``) or "auto" (``strength`` scaled by how
+        dark the frame is, :meth:`set_levels`), or its number."""
+        if isinstance(mode, str):
+            if mode not in ENHANCE_MODES:
+                raise ValueError(f"mode must be one of {ENHANCE_MODES}, got {mode!r}")
+            mode = ENHANCE_MODES.index(mode)
+        return self._set(camera, "mode", mode)
+
+    def set_strength(self, strength: int, camera=None) -> "FrameEnhance":
+        """Blend weight in 1/256, 0..256 (:func:`enhance_strength_q`)."""
+        return self._set(camera, "strength", strength)
+
+    def set_clip(self, clip: float, camera=None) -> "FrameEnhance":
+        """Clip limit as a multiple of the flat histogram's bin height, 1.0..64.0."""
+        if isinstance(clip, bool) or not 1.0 <= float(clip) <= 64.0:
+            raise ValueError(f"clip {clip!r} outside 1.0..64.0")
+        return self._set(camera, "clip_q8", int(float(clip) * 256 + 0.5))
+
+    def set_levels(self, dark: float, bright: float, camera=None) -> "FrameEnhance":
+        """Auto mode's ramp in luma levels: full strength at a mean luma of ``dark`` or below,
+        none at ``bright`` or above; at least one level apart."""
+        lo16, hi16 = watch_level16(dark), watch_level16(bright)
+        if hi16 - lo16 < _ref.ENHANCE_MIN_SPAN:
+            raise ValueError(f"levels dark {dark} / bright {bright} are less than one luma "
+                             f"level apart")
+        # both checked before either is stored
+        for name, v in (("lo16", lo16), ("hi16", hi16)):
+            lo, hi = ENHANCE_PARAM_RANGES[ENHANCE_PARAMS.index(name)]
+            if not lo <= v <= hi:
+                raise ValueError(f"enhance parameter {name} = {v} outside {lo}..{hi}")
+        return self._set(camera, "lo16", lo16)._set(camera, "hi16", hi16)
+
+
+def frame_enhance(images: torch.Tensor, enh: FrameEnhance, slot0: int = 0,
+                  out: Optional[torch.Tensor] = None,
+                  out_stats: Optional[torch.Tensor] = None):
+    """Low-light enhancement of one step: batch row n of ``images`` -- uint8 RGB [N, H, W, 3]
+    -- is camera ``slot0 + n`` of ``enh``.  Contrast-limited adaptive histogram equalisation of
+    the luma on ``enh.tiles``, blended in at the camera's ``alpha`` (0..256); R, G and B move
+    by the same amount, so the chroma stays.  ``out`` None works in place (a camera whose
+    alpha is 0 is then not written at all), else every byte of ``out`` is written.  Returns
+    ``(out or images, stats)``, stats int32 [N, 2] = mean16 (mean luma in 1/16), alpha, every
+    element written.  Integer arithmetic: GPU (csrc/kernels/frame_enhance.hip) and CPU
+    (ops.reference.frame_enhance, where the rules are written out) are byte-identical."""
+    if not isinstance(enh, FrameEnhance):
+        raise TypeError(f"enh must be an ops.FrameEnhance, got {type(enh).__name__}")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"images are uint8 RGB [N, H, W, 3], got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    hw = (int(images.shape[1]), int(images.shape[2]))
+    if hw != enh.hw:
+        raise ValueError(f"images of {hw[0]}x{hw[1]}, the enhancer was made for "
+                         f"{enh.hw[0]}x{enh.hw[1]}")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    if images.device != enh.device:
+        raise ValueError(f"images on {images.device}, enhancer on {enh.device}")
+    n = int(images.shape[0])
+    slot0 = int(slot0)
+    if slot0 < 0 or slot0 + n > enh.streams:
+        raise ValueError(f"cameras [{slot0}, {slot0 + n}) outside the enhancer's {enh.streams}")
+    if out is not None and (out.dtype != torch.uint8 or out.shape != images.shape
+                            or not out.is_contiguous() or out.device != images.device):
+        raise ValueError(f"out must be contiguous uint8 {list(images.shape)} on {images.device}")
+    if out_stats is None:
+        out_stats = empty(n, 2, dtype=torch.int32, device=images.device)
+    if (out_stats.dtype != torch.int32 or tuple(out_stats.shape) != (n, 2)
+            or not out_stats.is_contiguous() or out_stats.device != images.device):
+        raise ValueError(f"out_stats must be contiguous int32 {[n, 2]} on {images.device}")
+    dst = images if out is None else out
+    if images.is_cuda:
+        _native().frame_enhance(images, dst, enh.params, enh.axis, enh.luts, enh.sums, out_stats,
+                                slot0, enh.tiles[0], enh.tiles[1], enh.hist_copies)
+    else:
+        _ref.frame_enhance(images, enh, slot0, out, out_stats)
+    return dst, out_stats
+
+
+# ---------------------------------------------------------------------------
 # motion regions: the watch's motion grid -> connected blobs as detection rows
 # ---------------------------------------------------------------------------
 BLOB_MAX_CELLS = _ref.BLOB_MAX_CELLS

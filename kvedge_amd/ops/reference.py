@@ -1231,3 +1231,118 @@ def motion_blobs(mask, params, ignore, slot0, cell, frame_hw, connectivity, out_
                  min((max(ys) + 1) * cell, hs), len(cells), cls], dtype=torch.float32)
             out_labels[n][torch.tensor(ys), torch.tensor(xs)] = r
     return out_det, out_count, out_labels
+
+
+# ---------------------------------------------------------------------------
+# low-light enhancement: per-camera CLAHE on luma, chroma kept
+# ---------------------------------------------------------------------------
+ENHANCE_MODES = ("off", "on", "auto")
+ENHANCE_PARAMS = ("mode", "strength", "clip_q8", "lo16", "hi16")
+# the ranges the kernel clamps the words into; hi16 is further kept >= lo16 + ENHANCE_MIN_SPAN
+ENHANCE_PARAM_RANGES = ((0, 2), (0, 256), (256, 16384), (0, 4080), (16, 4096))
+ENHANCE_MIN_SPAN = 16
+ENHANCE_MAX_TILES = 16
+ENHANCE_MAX_EXTENT = 4096
+
+
+def enhance_axis(size: int, tiles: int):
+    """Interpolation table of one axis of ``size`` pixels cut into ``tiles`` tiles of
+    s = ceil(size / tiles): int32 numpy (t0, t1, w), [size] each.  Pixel p lies between the
+    centres of tiles t0 and t1, w / 64 of the way to t1: a = 2 p + 1 - s; a <= 0: t0 = t1 = 0,
+    w = 0; else t0 = a // (2 s), and t0 >= tiles - 1: t0 = t1 = tiles - 1, w = 0; else
+    t1 = t0 + 1, w = ((a - 2 s t0) 64 + s) // (2 s) in 0..64."""
+    s = -(-size // tiles)
+    a = 2 * np.arange(size, dtype=np.int64) + 1 - s
+    t0 = np.clip(a // (2 * s), 0, tiles - 1)
+    edge = (a <= 0) | (t0 >= tiles - 1)
+    t1 = np.where(edge, t0, t0 + 1)
+    w = np.where(edge, 0, ((a - 2 * s * t0) * 64 + s) // (2 * s))
+    return t0.astype(np.int32), t1.astype(np.int32), w.astype(np.int32)
+
+
+def enhance_tile_table(hist, clip_q8: int):
+    """One tile's table from its histogram (int64 numpy [256], n = hist.sum() pixels):
+    L = max(1, (clip_q8 n) >> 16); the excess E = sum(max(hist - L, 0)) is clipped off and
+    handed back, E // 256 to every bin and, with r = E % 256 > 0 and step = 256 // r, one more
+    to the bins v % step == 0 with v // step < r, so the total is n again; c the inclusive
+    prefix sum; lut[v] = (255 c[v] + n // 2) // n.  Returns (lut uint8 [256], the
+    redistributed histogram)."""
+    hist = np.asarray(hist, dtype=np.int64)
+    n = int(hist.sum())
+    L = max(1, (int(clip_q8) * n) >> 16)
+    E = int(np.maximum(hist - L, 0).sum())
+    h = np.minimum(hist, L) + E // 256
+    r = E % 256
+    if r:
+        v = np.arange(256)
+        step = 256 // r
+        h = h + ((v % step == 0) & (v // step < r))
+    c = np.cumsum(h)
+    return ((255 * c + n // 2) // n).astype(np.uint8), h
+
+
+def enhance_params(row):
+    """A camera's parameter words clamped the way the kernel clamps them:
+    (mode, strength, clip_q8, lo16, hi16)."""
+    mode, strength, clip_q8, lo16, hi16 = (
+        min(max(int(p), lo), hi) for p, (lo, hi) in zip(row, ENHANCE_PARAM_RANGES))
+    return mode, strength, clip_q8, lo16, max(hi16, lo16 + ENHANCE_MIN_SPAN)
+
+
+def enhance_alpha(mean16: int, mode: int, strength: int, lo16: int, hi16: int) -> int:
+    """Blend weight in 0..256: 0 off, ``strength`` on, and in auto ``strength`` scaled by a
+    ramp that is 256 at or below lo16 and 0 at or above hi16."""
+    if mode == 0:
+        return 0
+    if mode == 1:
+        return strength
+    ramp = min(max((hi16 - mean16) * 256 // (hi16 - lo16), 0), 256)
+    return (strength * ramp) >> 8
+
+
+def frame_enhance(images, enh, slot0, out, out_stats):
+    """Low-light enhancement: THE definition the HIP kernel (csrc/kernels/frame_enhance.hip)
+    equals byte for byte.  ``images`` uint8 RGB [N, H, W, 3], ``enh`` an ops.FrameEnhance on
+    the CPU (the tile grid and the per-camera words ``params``), row n is camera ``slot0 + n``;
+    ``out`` None works in place.  All integer.
+
+    Y = watch_luma.  The frame is cut into TY x TX tiles of th = ceil(H / TY) by
+    tw = ceil(W / TX) pixels (the last of an axis may be partial); every tile gets a table
+    (enhance_tile_table) from its own histogram.  A pixel reads the tables of the four tiles
+    whose centres surround it (enhance_axis per axis): A, B, C, D = lut[t0y, t0x][Y],
+    lut[t0y, t1x][Y], lut[t1y, t0x][Y], lut[t1y, t1x][Y] and
+    Y' = ((64 - wy) ((64 - wx) A + wx B) + wy ((64 - wx) C + wx D) + 2048) >> 12.
+    Per camera mean16 = (16 sum(Y) + P // 2) // P over its P pixels and alpha = enhance_alpha.
+    d = ((Y' - Y) alpha) >> 8 (floor) is added to R, G and B alike, each clamped into 0..255:
+    Y moves, Cb / Cr stay.  alpha == 0 in place leaves the camera's bytes alone.
+    out_stats int32 [N, 2] = mean16, alpha."""
+    N, H, W, _ = images.shape
+    TY, TX = enh.tiles
+    th, tw = -(-H // TY), -(-W // TX)
+    t0y, t1y, wy = (torch.from_numpy(a).to(torch.int64)[:, None] for a in enhance_axis(H, TY))
+    t0x, t1x, wx = (torch.from_numpy(a).to(torch.int64)[None, :] for a in enhance_axis(W, TX))
+    dst = images if out is None else out
+    for n in range(N):
+        mode, strength, clip_q8, lo16, hi16 = enhance_params(enh.params[slot0 + n].tolist())
+        rgb = images[n].to(torch.int32)
+        Y = watch_luma(images[n:n + 1])[0].to(torch.int64)
+        mean16 = (16 * int(Y.sum()) + H * W // 2) // (H * W)
+        alpha = enhance_alpha(mean16, mode, strength, lo16, hi16)
+        out_stats[n, 0], out_stats[n, 1] = mean16, alpha
+        if alpha == 0:
+            if out is not None:
+                out[n] = images[n]
+            continue
+        lut = np.empty((TY, TX, 256), dtype=np.int64)
+        for ty in range(TY):
+            for tx in range(TX):
+                tile = Y[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw].numpy()
+                lut[ty, tx] = enhance_tile_table(np.bincount(tile.ravel(), minlength=256),
+                                                 clip_q8)[0]
+        lut = torch.from_numpy(lut)
+        A, B = lut[t0y, t0x, Y], lut[t0y, t1x, Y]
+        C, D = lut[t1y, t0x, Y], lut[t1y, t1x, Y]
+        Y2 = ((64 - wy) * ((64 - wx) * A + wx * B) + wy * ((64 - wx) * C + wx * D) + 2048) >> 12
+        d = (((Y2 - Y) * alpha) >> 8).to(torch.int32)
+        dst[n] = (rgb + d[..., None]).clamp_(0, 255).to(torch.uint8)
+    return dst, out_stats
