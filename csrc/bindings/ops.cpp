@@ -1250,6 +1250,76 @@ void motion_blobs(const at::Tensor& mask, const at::Tensor& params, const at::Te
   TORCH_CHECK(rc == 0, "kvedge: motion_blobs failed rc=", rc);
 }
 
+// K27: appearance search (csrc/kernels/gallery.hip).  Everything is validated before a launch:
+// a rejected call leaves its outputs untouched.
+void embed_quantize(const at::Tensor& x, at::Tensor& codes, at::Tensor& nrm2) {
+  check_bf16(x, "features");
+  check_dev(codes, "codes");
+  check_dev(nrm2, "nrm2");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(), "kvedge: embed_quantize features bf16 [M,H,W,C]");
+  const int64_t M = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+  TORCH_CHECK(C >= 64 && C <= 4096 && C % 64 == 0,
+              "kvedge: embed_quantize C is a multiple of 64 in 64..4096, got ", C);
+  TORCH_CHECK(HW >= 1 && HW <= 256, "kvedge: embed_quantize H*W is 1..256, got ", HW);
+  TORCH_CHECK(M <= 65535, "kvedge: embed_quantize M <= 65535, got ", M);
+  TORCH_CHECK(codes.scalar_type() == at::kChar && codes.dim() == 2 && codes.size(0) == M &&
+                  codes.size(1) == C && codes.is_contiguous(),
+              "kvedge: embed_quantize codes int8 [M,C]");
+  TORCH_CHECK(nrm2.scalar_type() == at::kInt && nrm2.dim() == 1 && nrm2.size(0) == M &&
+                  nrm2.is_contiguous(), "kvedge: embed_quantize nrm2 int32 [M]");
+  TORCH_CHECK(x.device() == codes.device() && x.device() == nrm2.device(),
+              "kvedge: embed_quantize operands on different devices");
+  const c10::DeviceGuard g(x.device());
+  const int rc = kv_embed_quantize(x.data_ptr(), codes.data_ptr<int8_t>(), nrm2.data_ptr<int>(),
+                                   (int)M, (int)HW, (int)C, cur_stream(x));
+  TORCH_CHECK(rc == 0, "kvedge: embed_quantize failed rc=", rc);
+}
+
+int64_t gallery_workgroups(int64_t cap) {
+  TORCH_CHECK(cap >= 1 && cap <= (1 << 20), "kvedge: gallery_match capacity is 1..2^20, got ", cap);
+  return kv_gallery_workgroups((int)cap);
+}
+
+void gallery_match(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& scale,
+                   const at::Tensor& count, at::Tensor& part, at::Tensor& score,
+                   at::Tensor& row) {
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{
+           &q, &codes, &scale, &count, &part, &score, &row}) {
+    check_dev(*t, "operand");
+    TORCH_CHECK(t->is_contiguous(), "kvedge: gallery_match operands are contiguous");
+    TORCH_CHECK(t->device() == q.device(), "kvedge: gallery_match operands on different devices");
+  }
+  TORCH_CHECK(q.scalar_type() == at::kChar && q.dim() == 2, "kvedge: gallery_match q int8 [M,D]");
+  const int64_t M = q.size(0), D = q.size(1);
+  TORCH_CHECK(D >= 64 && D <= 4096 && D % 64 == 0,
+              "kvedge: gallery_match D is a multiple of 64 in 64..4096, got ", D);
+  TORCH_CHECK(M >= 1 && M <= 65535, "kvedge: gallery_match M is 1..65535, got ", M);
+  TORCH_CHECK(codes.scalar_type() == at::kChar && codes.dim() == 2 && codes.size(1) == D,
+              "kvedge: gallery_match codes int8 [cap,D]");
+  const int64_t cap = codes.size(0);
+  TORCH_CHECK(cap >= 1 && cap <= (1 << 20), "kvedge: gallery_match capacity is 1..2^20, got ", cap);
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.dim() == 1 && scale.size(0) == cap,
+              "kvedge: gallery_match scale fp32 [cap]");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == 1,
+              "kvedge: gallery_match count int32 [1]");
+  TORCH_CHECK(score.scalar_type() == at::kFloat && score.dim() == 2 && score.size(0) == M,
+              "kvedge: gallery_match score fp32 [M,K]");
+  const int64_t K = score.size(1);
+  TORCH_CHECK(K >= 1 && K <= 8, "kvedge: gallery_match top is 1..8, got ", K);
+  TORCH_CHECK(row.scalar_type() == at::kInt && row.sizes() == score.sizes(),
+              "kvedge: gallery_match row int32 [M,K]");
+  const int64_t need = M * kv_gallery_workgroups((int)cap) * K * 2;
+  TORCH_CHECK(part.scalar_type() == at::kInt && part.numel() >= need,
+              "kvedge: gallery_match workspace int32 of at least ", need, " elements");
+  const c10::DeviceGuard g(q.device());
+  const int rc = kv_gallery_match(q.data_ptr<int8_t>(), codes.data_ptr<int8_t>(),
+                                  scale.data_ptr<float>(), count.data_ptr<int>(), part.data_ptr(),
+                                  (long long)part.numel() * 4, score.data_ptr<float>(),
+                                  row.data_ptr<int>(), (int)M, (int)D, (int)cap, (int)K,
+                                  cur_stream(q));
+  TORCH_CHECK(rc == 0, "kvedge: gallery_match failed rc=", rc);
+}
+
 void batchnorm_nhwc(const at::Tensor& x, at::Tensor& y, const at::Tensor& scale,
                     const at::Tensor& shift, bool relu) {
   check_bf16(x, "x");
@@ -1389,6 +1459,10 @@ TORCH_LIBRARY(kvedge, m) {
         "Tensor? track_id, int Hs, int Ws, int slot0) -> ()");
   m.def("motion_blobs(Tensor mask, Tensor params, Tensor ignore, Tensor(a!) det, Tensor(b!) count, "
         "Tensor(c!) labels, int slot0, int cell, int Hs, int Ws, int connectivity) -> ()");
+  m.def("embed_quantize(Tensor features, Tensor(a!) codes, Tensor(b!) nrm2) -> ()");
+  m.def("gallery_match(Tensor q, Tensor codes, Tensor scale, Tensor count, Tensor(a!) part, "
+        "Tensor(b!) score, Tensor(c!) row) -> ()");
+  m.def("gallery_workgroups(int cap) -> int", gallery_workgroups);
   m.def("batchnorm_nhwc(Tensor x, Tensor(a!) y, Tensor scale, Tensor shift, bool relu) -> ()");
   m.def("conv_num_tiles() -> int", conv_num_tiles);
   m.def("conv_splitk_base() -> int", conv_splitk_base);
@@ -1442,6 +1516,8 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("jpeg_encode", jpeg_encode);
   m.impl("annotate", annotate);
   m.impl("motion_blobs", motion_blobs);
+  m.impl("embed_quantize", embed_quantize);
+  m.impl("gallery_match", gallery_match);
   m.impl("batchnorm_nhwc", batchnorm_nhwc);
 }
 

@@ -316,6 +316,26 @@ int kv_motion_blobs_max_cells(void);
 int kv_motion_blobs(const unsigned char* mask, const int* params, const unsigned char* ignore,
                     float* det, int* count, int* labels, int N, int S, int slot0, int Hs, int Ws,
                     int cell, int max_blobs, int connectivity, hipStream_t s);
+// K27 (gallery.hip): appearance search, all integer, bit-identical to ops.reference.
+// kv_embed_quantize: x bf16 [M,HW,C] -> codes int8 [M,C], nrm2 int32 [M] (average pooling as an
+// int32 sum of rintf(clamp(x) * 256) plus block-floating-point quantisation to 7 bits; the rule
+// is at the top of gallery.hip).  One workgroup per row.  Returns -1 C outside 64..4096 or
+// C % 64, -2 HW outside 1..256, -3 M outside 0..65535, -7 misaligned operand.
+// kv_gallery_match: q int8 [M,D] against codes int8 [cap,D] with scale fp32 [cap] and the live
+// row count int32 [1] in device memory: score fp32 [M,K] / row int32 [M,K] = the K best rows
+// j < min(count, cap) with scale[j] > 0 by (float)dot_i32 * scale[j], score descending then row
+// ascending; empty slots score 0 row -1; every element written.  Two launches: persistent
+// workgroups over 128-row gallery blocks (i8 MFMA, top-K fused) write part = [M,
+// kv_gallery_workgroups(cap), K] (score, row) pairs, 8 bytes each, then one wavefront per query
+// merges them.  part is the caller's workspace of part_bytes.  Returns -1 D outside 64..4096 or
+// D % 64, -2 M outside 1..65535, -3 cap outside 1..2^20, -4 K outside 1..8, -5 part too small,
+// -7 misaligned operand; nothing is written then.
+int kv_embed_quantize(const void* x, signed char* codes, int* nrm2, int M, int HW, int C,
+                      hipStream_t s);
+int kv_gallery_workgroups(int cap);
+int kv_gallery_match(const signed char* q, const signed char* codes, const float* scale,
+                     const int* count, void* part, long long part_bytes, float* score, int* row,
+                     int M, int D, int cap, int K, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

@@ -102,7 +102,7 @@ if os.environ.get("KVEDGE_VARIANT"):
 # (six int -> float conversions per det row) and its code has no v_pk_* with or without the
 # flag.  -Xclang reaches the host pass too, which reports the feature as unknown and ignores it.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"motion_blobs.hip": NO_PACKED_FP32}
+EXTRA = {"motion_blobs.hip": NO_PACKED_FP32, "gallery.hip": NO_PACKED_FP32}
 
 
 def build(force: bool = False, jobs: int = 0, verbose: bool = False, asan: bool = False) -> str:

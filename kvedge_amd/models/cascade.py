@@ -27,12 +27,23 @@ class KvDetectClassify:
     """frames u8 [N,640,640,3] -> (det fp32 [N,max_det,6], count int32 [N],
     crop_cls int64 [N,K], crop_prob fp32 [N,K]).  ``crop_cls[n, k]`` / ``crop_prob[n, k]``
     are the classifier's top-1 class and its probability for detection row k of image n
-    (rows are ordered by score); -1 / 0 where k >= count[n]."""
+    (rows are ordered by score); -1 / 0 where k >= count[n].
+
+    ``gallery`` (an ops.Gallery of the classifier's 2048-wide embeddings): appearance search.
+    The classifier's feature map of every crop, computed once, also becomes an int8 embedding
+    (ops.embed_quantize) that is matched to the gallery (ops.gallery_match), and the outputs
+    gain, directly after crop_prob, ``match_label`` int32 [N,K,gallery_top] (the enrolled label
+    of the best rows, -1 = none) and ``match_cos`` fp32 [N,K,gallery_top] (their cosine, 0
+    where none).  A match below ``gallery_threshold`` counts as none; the threshold lives in a
+    device word (:meth:`set_gallery_threshold`), and the gallery's rows and count are read at
+    run time, so enrolling, removing and a new threshold need no recapture."""
 
     image_size = 640
+    embed_dim = 2048
 
     def __init__(self, detector: KvYoloV8n, classifier: KvResNet50, crops_per_image: int,
-                 crop_size: int = 224):
+                 crop_size: int = 224, gallery=None, gallery_top: int = 1,
+                 gallery_threshold: float = 0.5):
         if not 1 <= crops_per_image <= detector.max_det:
             raise ValueError(f"crops_per_image must be 1..max_det = {detector.max_det}, "
                              f"got {crops_per_image}")
@@ -42,6 +53,27 @@ class KvDetectClassify:
         self.k, self.crop_size = int(crops_per_image), int(crop_size)
         self.device = detector.device
         self._slots = torch.arange(self.k, device=self.device).view(1, self.k)
+        self.gallery = gallery
+        self.embedding = None  # (codes int8 [N*K, 2048], nrm2 int32 [N*K]) of the last step
+        if gallery is not None:
+            if not isinstance(gallery, ops.Gallery):
+                raise TypeError(f"gallery must be an ops.Gallery, got {type(gallery).__name__}")
+            if gallery.dim != self.embed_dim or gallery.device.type != self.device.type:
+                raise ValueError(f"the gallery must hold {self.embed_dim}-wide rows on "
+                                 f"{self.device}, got {gallery.dim} on {gallery.device}")
+            if isinstance(gallery_top, bool) or not 1 <= int(gallery_top) <= ops.GALLERY_MAX_TOP:
+                raise ValueError(f"gallery_top must be 1..{ops.GALLERY_MAX_TOP}, "
+                                 f"got {gallery_top!r}")
+            self.gallery_top = int(gallery_top)
+            self._threshold = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.set_gallery_threshold(gallery_threshold)
+
+    def set_gallery_threshold(self, v: float) -> "KvDetectClassify":
+        """Matches of cosine below ``v`` (-1..1) report no label, from the next step on."""
+        if isinstance(v, bool) or not -1.0 <= float(v) <= 1.0:
+            raise ValueError(f"gallery_threshold must be -1..1, got {v!r}")
+        self._threshold.copy_(torch.tensor([float(v)], dtype=torch.float32))
+        return self
 
     def convs(self) -> List:
         return self.detector.convs() + self.classifier.convs()
@@ -63,17 +95,35 @@ class KvDetectClassify:
         n = src_u8.shape[0]
         crops = ops.roi_crop(src_u8, det, count, self.k, self.crop_size, pad=CROP_PAD,
                              src_format=src_format)
-        probs, top1 = self.classifier(crops)
+        if self.gallery is None:
+            probs, top1 = self.classifier(crops)
+        else:  # one pass through the backbone: its map feeds the logits and the embedding
+            feat = self.classifier.raw_features(crops)
+            probs, top1 = ops.softmax_rows(self.classifier.head(feat))
         top1 = top1.view(n, self.k)
         prob = probs.gather(1, top1.view(-1, 1)).view(n, self.k)
         invalid = self._slots >= count.view(n, 1)
-        return top1.masked_fill(invalid, -1), prob.masked_fill(invalid, 0.0)
+        out = (top1.masked_fill(invalid, -1), prob.masked_fill(invalid, 0.0))
+        if self.gallery is None:
+            return out
+        return out + self.match(feat, invalid)
+
+    def match(self, feat: torch.Tensor, invalid: torch.Tensor):
+        """The crops' feature maps -> (match_label, match_cos) [N, K, top]."""
+        n, t = invalid.shape[0], self.gallery_top
+        codes, nrm2 = ops.embed_quantize(feat)
+        self.embedding = (codes, nrm2)
+        score, row = ops.gallery_match(codes, self.gallery, t)
+        cos = score * torch.rsqrt(nrm2.to(torch.float32).clamp_(min=1.0)).view(-1, 1)
+        label = self.gallery.label[row.clamp(min=0).long()]
+        none = (row < 0) | (cos < self._threshold) | invalid.reshape(-1, 1)
+        return (label.masked_fill(none, -1).view(n, self.k, t),
+                cos.masked_fill(none, 0.0).view(n, self.k, t))
 
     def __call__(self, frames_u8: torch.Tensor):
         """Model-size frames: the crops come from the frames the detector saw."""
         det, count = self.detector(frames_u8)
-        crop_cls, crop_prob = self.classify(frames_u8, det, count)
-        return det, count, crop_cls, crop_prob
+        return (det, count) + self.classify(frames_u8, det, count)
 
     def from_source(self, source_frames: torch.Tensor, frames: torch.Tensor,
                     plan: "ops.ResizePlan", src_format: str = "rgb"):
@@ -81,5 +131,4 @@ class KvDetectClassify:
         ``frames``, map the kept boxes to frame pixels, cut the crops from ``source_frames``
         at full resolution (``src_format="nv12"``: from the NV12 frames)."""
         det, count = self.detector.to_source(self.detector(frames), plan)
-        crop_cls, crop_prob = self.classify(source_frames, det, count, src_format=src_format)
-        return det, count, crop_cls, crop_prob
+        return (det, count) + self.classify(source_frames, det, count, src_format=src_format)

@@ -318,7 +318,10 @@ class KvResNet50:
         return x
 
     def logits(self, x: torch.Tensor, frames_in: bool = False) -> torch.Tensor:
-        f = self.features(x, frames_in)
+        return self.head(self.features(x, frames_in))
+
+    def head(self, f: torch.Tensor) -> torch.Tensor:
+        """The feature map of :meth:`features` -> pre-softmax logits [B, C]."""
         B = f.shape[0]
         if f.is_cuda and B <= ops.POOLED_FC_MAX_BATCH and self.fuse_head:
             return ops.pooled_fc(f, self.fc.w, self.fc.b)  # one GEMV launch at edge batches
@@ -335,6 +338,13 @@ class KvResNet50:
         if self.fuse_preprocess and self.fuse_stem_pool and frames_u8.is_cuda:
             return self.logits(frames_u8, frames_in=True)
         return self.logits(self.preprocess(frames_u8))
+
+    def raw_features(self, frames_u8: torch.Tensor) -> torch.Tensor:
+        """uint8 frames -> the final feature map, by the kernel path of :meth:`raw_outputs`:
+        ``head(raw_features(x))`` is ``raw_outputs(x)``."""
+        if self.fuse_preprocess and self.fuse_stem_pool and frames_u8.is_cuda:
+            return self.features(frames_u8, frames_in=True)
+        return self.features(self.preprocess(frames_u8))
 
     def __call__(self, frames_u8: torch.Tensor, out: Optional[dict] = None):
         lg = self.raw_outputs(frames_u8)

@@ -180,6 +180,13 @@ def main(argv=None):
                     help="low-light enhancement (CLAHE on luma) of the model-size frames on the "
                          "device: `on` for every camera, `auto` for dark ones (twin keys "
                          "`enhance`, `enhance_mode`; telemetry gains `enhanced`)")
+    ap.add_argument("--gallery", default=d.gallery,
+                    help="--model detect-classify: .npz of enrolled embeddings (ops.Gallery.save; "
+                         "a new path starts empty); every crop is matched to it on the device "
+                         "(twin keys `gallery`, `gallery_top`, `gallery_threshold`; telemetry "
+                         "gains `matches`; direct methods gallery_enrol / gallery_remove)")
+    ap.add_argument("--gallery-top", type=int, default=d.gallery_top)
+    ap.add_argument("--gallery-threshold", type=float, default=d.gallery_threshold)
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -240,6 +247,8 @@ def main(argv=None):
                        snapshot_labels=a.snapshot_labels,
                        snapshot_privacy_classes=a.privacy_classes,
                        snapshot_privacy_zones=a.privacy_zones_json,
+                       gallery=a.gallery, gallery_top=a.gallery_top,
+                       gallery_threshold=a.gallery_threshold,
                        enhance=bool(a.enhance),
                        enhance_mode=a.enhance or d.enhance_mode).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub

@@ -409,6 +409,7 @@ class ModuleApp:
         self.snapshots = None
         self.views = None
         self.enhance = None
+        self.cascade = self.match_totals = None  # KvDetectClassify(gallery=...) and its totals
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         if cfg.model == "simulated-temperature":
@@ -432,7 +433,16 @@ class ModuleApp:
                 from ..models.resnet import KvResNet50
 
                 clf = KvResNet50.build(seed=cfg.seed, device=dev, calibrate=dev.type == "cuda")
-                self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
+                if cfg.gallery:  # appearance search: match_label / match_cos after crop_prob
+                    from .gallery import MatchTotals, build_gallery
+
+                    self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image,
+                                                  gallery=build_gallery(cfg, dev),
+                                                  gallery_top=cfg.gallery_top,
+                                                  gallery_threshold=cfg.gallery_threshold)
+                    self.cascade, self.match_totals = self.model, MatchTotals()
+                else:
+                    self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
             if cfg.track:
                 from ..models.tracking import KvTracked
 
@@ -493,7 +503,10 @@ class ModuleApp:
         self.engine = InferenceEngine(self.model, cfg.batch, cfg.resolved_image_size(), device=dev,
                                       seed=cfg.seed + self.rank, use_graph=cfg.use_graph,
                                       synthetic=not camera,
-                                      streams=edge_streams(cfg.batch) if dev.type == "cuda" else 1,
+                                      # a gallery keeps the crops' embeddings of ONE whole batch
+                                      # for gallery_enrol: one stream
+                                      streams=(edge_streams(cfg.batch)
+                                               if dev.type == "cuda" and not cfg.gallery else 1),
                                       frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format(),
                                       views=self.views, enhance=self.enhance)
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
@@ -826,6 +839,8 @@ class ModuleApp:
             order = counts.argsort(descending=True)[:5]
             res["crops"] = int(cls.numel())
             res["crop_top1"] = {str(int(vals[i])): int(counts[i]) for i in order}
+            if getattr(self, "match_totals", None) is not None:
+                res.update(self.match_totals.summary(out[4], out[5]))
         if self.cfg.track and getattr(self.model, "stateful", False):
             st = self.model.state  # live tracks, distinct confirmed objects, lost detections
             res["tracks"] = {"active": st.active(), "unique": st.unique(),
@@ -905,6 +920,10 @@ class ModuleApp:
                         for k in ModuleConfig.ENHANCE_LIVE_KEYS)):
             # the enhancement words too: the next replay reads the new ones
             self._apply_enhance(self.cfg)
+        if (getattr(self, "cascade", None) is not None and not self.cfg.needs_rebuild(old)
+                and self.cfg.gallery_threshold != old.gallery_threshold):
+            # the match threshold is a device word too
+            self.cascade.set_gallery_threshold(self.cfg.gallery_threshold)
         if (self.snapshots is not None and not self.cfg.needs_rebuild(old)
                 and self.cfg.snapshot_quality != old.snapshot_quality):
             # the quantisation tables live in device memory, like the watch thresholds
@@ -1000,6 +1019,14 @@ class ModuleApp:
                     return 400, {"error": "snapshots are off"}
                 return self.snapshots.method(self.engine.outputs, payload,
                                              self.cfg.snapshot_max_bytes)
+            if name in ("gallery_enrol", "gallery_remove"):
+                if getattr(self, "cascade", None) is None:
+                    return 400, {"error": "no gallery configured"}
+                from . import gallery as _gallery
+
+                if name == "gallery_enrol":
+                    return _gallery.enrol(self.cascade, self.cfg.batch, payload or {})
+                return _gallery.remove(self.cascade, payload or {})
             if name in ("reconfigure", "benchmark"):
                 if self.rank != 0:
                     return 409, {"error": NOT_CONTROL_POINT.format(rank=self.rank)}

@@ -252,7 +252,14 @@ class ModuleConfig:
     enhance_clip: float = 2.0
     enhance_dark_level: float = 24.0
     enhance_bright_level: float = 64.0
-    native_loop: bool = True    # GPU: replay the graph from the C++ serve loop
+    # appearance search (model "detect-classify"): `gallery` is the path of an .npz written by
+    # ops.Gallery.save; every crop's embedding is matched to it on the device and the
+    # gallery_top (1..8) best labels of cosine >= gallery_threshold are reported.  Only the
+    # threshold is live (a device word); the other two need a rebuild
+    gallery: str = ""
+    gallery_top: int = 1
+    gallery_threshold: float = 0.5
+    native_loop: bool = True   # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
     # 0 = off, the default).  It times runner-up tiles inside the captured step; on the
@@ -275,7 +282,7 @@ class ModuleConfig:
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
                "watch_bg_shift", "watch_regions", "watch_region_max",
                "watch_region_connectivity", "snapshots", "snapshot_width", "snapshot_subsampling",
-               "snapshot_annotate", "enhance")
+               "snapshot_annotate", "enhance", "gallery", "gallery_top")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
@@ -471,6 +478,13 @@ class ModuleConfig:
                              "least one level above it, at most 256")
         if self.enhance and self.model == "simulated-temperature":
             raise ValueError("enhance needs frames: a vision model")
+        # appearance search (ops.Gallery / ops.gallery_match)
+        if not 1 <= self.gallery_top <= 8:
+            raise ValueError("gallery_top must be 1..8")
+        if not -1.0 <= self.gallery_threshold <= 1.0:
+            raise ValueError("gallery_threshold must be -1..1")
+        if self.gallery and self.model != "detect-classify":
+            raise ValueError("gallery needs crops to embed: model detect-classify")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -562,6 +576,8 @@ class ModuleConfig:
                          "enhance_dark_level", "enhance_bright_level")
     ENHANCE_KEYS = ("enhance",) + ENHANCE_LIVE_KEYS
 
+    GALLERY_KEYS = ("gallery", "gallery_top", "gallery_threshold")
+
     SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
                      "snapshot_every_s", "snapshot_max_bytes")
 
@@ -629,5 +645,9 @@ class ModuleConfig:
         # and the enhancement keys
         if all(getattr(self, k) == getattr(base, k) for k in self.ENHANCE_KEYS):
             for k in self.ENHANCE_KEYS:
+                d.pop(k)
+        # and the appearance-search keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.GALLERY_KEYS):
+            for k in self.GALLERY_KEYS:
                 d.pop(k)
         return d

@@ -2051,6 +2051,224 @@ def motion_blobs(mask: torch.Tensor, regions: MotionRegions, slot0: int = 0, max
 
 
 # ---------------------------------------------------------------------------
+# appearance search: int8 embeddings of the crops matched to a gallery on the device
+# ---------------------------------------------------------------------------
+GALLERY_MAX_CAPACITY = 1 << 20
+GALLERY_MAX_TOP = 8
+GALLERY_MAX_QUERIES = 65535
+
+
+def _check_embed_dim(d: int) -> int:
+    if isinstance(d, bool) or not (64 <= int(d) <= 4096 and int(d) % 64 == 0):
+        raise ValueError(f"the embedding width is a multiple of 64 in 64..4096, got {d!r}")
+    return int(d)
+
+
+def _check_out(name, t, dt, shape, device):
+    if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be contiguous {dt} {list(shape)} on {device}")
+
+
+def embed_quantize(features: torch.Tensor, out_codes: Optional[torch.Tensor] = None,
+                   out_nrm2: Optional[torch.Tensor] = None):
+    """Feature maps bf16 [M, H, W, C] (NHWC, contiguous; C % 64 == 0 in 64..4096, H W in
+    1..256) -> ``(codes, nrm2)``: int8 [M, C] and int32 [M] = sum codes^2.  Average pooling as
+    an exact int32 sum of rint(clamp(x) * 256), then one shared exponent per row so that the
+    largest channel lands in 64..127 (ops.reference.embed_quantize writes the rule out).  GPU
+    (csrc/kernels/gallery.hip) and CPU are bit-identical; one launch, capturable."""
+    if features.dtype != torch.bfloat16 or features.dim() != 4 or not features.is_contiguous():
+        raise ValueError(f"features must be contiguous bf16 [M, H, W, C], got {features.dtype} "
+                         f"{tuple(features.shape)}")
+    m, h, w, c = (int(v) for v in features.shape)
+    _check_embed_dim(c)
+    if not 1 <= h * w <= 256:
+        raise ValueError(f"embed_quantize pools 1..256 positions, got {h}x{w}")
+    if m > GALLERY_MAX_QUERIES:
+        raise ValueError(f"at most {GALLERY_MAX_QUERIES} rows, got {m}")
+    dev = features.device
+    if out_codes is None:
+        out_codes = empty(m, c, dtype=torch.int8, device=dev)
+    if out_nrm2 is None:
+        out_nrm2 = empty(m, dtype=torch.int32, device=dev)
+    _check_out("out_codes", out_codes, torch.int8, (m, c), dev)
+    _check_out("out_nrm2", out_nrm2, torch.int32, (m,), dev)
+    if features.is_cuda:
+        _native().embed_quantize(features, out_codes, out_nrm2)
+    else:
+        _ref.embed_quantize(features, out_codes, out_nrm2)
+    return out_codes, out_nrm2
+
+
+class Gallery:
+    """The enrolled embeddings ops.gallery_match scores against, for up to ``capacity`` (1..2^20)
+    rows of ``dim`` int8 codes, in device memory with host mirrors: ``codes`` int8 [capacity,
+    dim], ``scale`` fp32 [capacity] = 1 / sqrt(nrm2) (computed on the host, so both sides read
+    the same bits), ``label`` int32 [capacity] and ``count`` int32 [1].  The kernel reads
+    ``count`` at run time: :meth:`enrol`, :meth:`remove` and :meth:`clear` take effect from the
+    next call, or the next replay of a captured step, without recapturing."""
+
+    def __init__(self, capacity: int, dim: int, device="cpu"):
+        if isinstance(capacity, bool) or not 1 <= int(capacity) <= GALLERY_MAX_CAPACITY:
+            raise ValueError(f"capacity must be 1..{GALLERY_MAX_CAPACITY}, got {capacity!r}")
+        self.capacity, self.dim = int(capacity), _check_embed_dim(dim)
+        cpu = torch.device(device).type == "cpu"
+        self._codes = torch.zeros(self.capacity, self.dim, dtype=torch.int8)
+        self._nrm2 = torch.zeros(self.capacity, dtype=torch.int32)
+        self._scale = torch.zeros(self.capacity, dtype=torch.float32)
+        self._label = torch.full((self.capacity,), -1, dtype=torch.int32)
+        self._count = torch.zeros(1, dtype=torch.int32)
+        self.codes = self._codes if cpu else self._codes.to(device)
+        self.scale = self._scale if cpu else self._scale.to(device)
+        self.label = self._label if cpu else self._label.to(device)
+        self.count = self._count if cpu else self._count.to(device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.codes.device
+
+    def __len__(self) -> int:
+        return int(self._count[0])
+
+    def labels(self) -> torch.Tensor:
+        """The enrolled rows' labels, int32 [len] (a host copy)."""
+        return self._label[:len(self)].clone()
+
+    def _upload(self, lo: int, hi: int) -> None:
+        """Rows [lo, hi) and the count to the device; the count goes last."""
+        if self.codes is not self._codes:
+            for dev, host in ((self.codes, self._codes), (self.scale, self._scale),
+                              (self.label, self._label)):
+                if hi > lo:
+                    dev[lo:hi].copy_(host[lo:hi])
+            self.count.copy_(self._count)
+
+    def enrol(self, codes, nrm2, label) -> "Gallery":
+        """Append rows: ``codes`` int8 [R, dim] (or [dim]), ``nrm2`` int32 [R] = sum codes^2 as
+        ops.embed_quantize returned it, ``label`` an int >= 0 or int [R].  A row of nrm2 == 0
+        has no direction and is refused; so is a row past the capacity."""
+        codes = torch.as_tensor(codes).detach().cpu()
+        if codes.dim() == 1:
+            codes = codes[None]
+        nrm2 = torch.as_tensor(nrm2).detach().cpu().reshape(-1).to(torch.int64)
+        r = int(codes.shape[0])
+        if codes.dtype != torch.int8 or codes.dim() != 2 or codes.shape[1] != self.dim:
+            raise ValueError(f"codes must be int8 [R, {self.dim}], got {codes.dtype} "
+                             f"{tuple(codes.shape)}")
+        label = torch.as_tensor(label).detach().cpu().reshape(-1).to(torch.int64)
+        if label.numel() == 1:
+            label = label.expand(r)
+        if nrm2.numel() != r or label.numel() != r:
+            raise ValueError(f"{r} rows of codes, {nrm2.numel()} of nrm2, {label.numel()} labels")
+        if not torch.equal(nrm2, (codes.long() ** 2).sum(1)):
+            raise ValueError("nrm2 is not the sum of the codes' squares")
+        if bool((nrm2 == 0).any()):
+            raise ValueError("a row with nrm2 == 0 cannot be enrolled")
+        if bool((label < 0).any()) or bool((label >= 2 ** 31).any()):
+            raise ValueError("labels are 0..2^31-1")
+        lo = len(self)
+        if lo + r > self.capacity:
+            raise ValueError(f"the gallery holds {self.capacity} rows; {lo} enrolled, {r} more asked")
+        self._codes[lo:lo + r] = codes
+        self._nrm2[lo:lo + r] = nrm2.to(torch.int32)
+        self._scale[lo:lo + r] = 1.0 / torch.sqrt(nrm2.to(torch.float32))
+        self._label[lo:lo + r] = label.to(torch.int32)
+        self._count[0] = lo + r
+        self._upload(lo, lo + r)
+        return self
+
+    def remove(self, label: int) -> int:
+        """Drop every row of ``label``, close the gaps (the order of the rest is kept) and lower
+        ``count``; returns the number of rows dropped."""
+        n = len(self)
+        keep = torch.nonzero(self._label[:n] != int(label)).reshape(-1)
+        k = int(keep.numel())
+        if k == n:
+            return 0
+        for host in (self._codes, self._nrm2, self._scale, self._label):
+            host[:k] = host[keep]
+        self._scale[k:n] = 0.0
+        self._label[k:n] = -1
+        self._count[0] = k
+        self._upload(0, n)
+        return n - k
+
+    def clear(self) -> "Gallery":
+        n = len(self)
+        self._scale[:n] = 0.0
+        self._label[:n] = -1
+        self._count[0] = 0
+        self._upload(0, n)
+        return self
+
+    def save(self, path) -> None:
+        """codes, nrm2 and labels of the enrolled rows as an ``.npz``."""
+        import numpy as np
+        n = len(self)
+        with open(path, "wb") as f:
+            np.savez(f, codes=self._codes[:n].numpy(), nrm2=self._nrm2[:n].numpy(),
+                     labels=self._label[:n].numpy())
+
+    @staticmethod
+    def load(path, capacity: int = 0, device="cpu") -> "Gallery":
+        """The gallery of an ``.npz`` written by :meth:`save`; ``capacity`` 0 = its rows (at
+        least 1)."""
+        import numpy as np
+        with np.load(path) as z:
+            codes, nrm2, labels = (torch.from_numpy(z[k].copy()) for k in ("codes", "nrm2", "labels"))
+        if codes.dim() != 2 or codes.dtype != torch.int8:
+            raise ValueError(f"{path}: codes must be int8 [R, dim]")
+        g = Gallery(capacity or max(1, int(codes.shape[0])), int(codes.shape[1]), device)
+        if codes.shape[0]:
+            g.enrol(codes, nrm2, labels)
+        return g
+
+
+def gallery_match(q_codes: torch.Tensor, gallery: Gallery, top: int = 1,
+                  out_score: Optional[torch.Tensor] = None,
+                  out_row: Optional[torch.Tensor] = None):
+    """The ``top`` (1..8) best rows of ``gallery`` for every query of ``q_codes`` int8 [M, dim]
+    (M in 1..65535).  Returns ``(score, row)``: fp32 [M, top] = float32(integer dot product) *
+    gallery.scale[row] and int32 [M, top], ordered by score descending, then row ascending;
+    slots past the number of enrolled rows hold 0 / -1.  ``score * rsqrt(nrm2 of the query)``
+    is the cosine.  The gallery's count is read on the device at run time.  Two launches, no
+    host synchronisation, capturable (csrc/kernels/gallery.hip: i8 MFMA, the gallery is read
+    once for M <= 256); GPU and CPU (ops.reference.gallery_match) are bit-identical."""
+    if not isinstance(gallery, Gallery):
+        raise TypeError(f"gallery must be an ops.Gallery, got {type(gallery).__name__}")
+    if q_codes.dtype != torch.int8 or q_codes.dim() != 2 or not q_codes.is_contiguous():
+        raise ValueError(f"q_codes must be contiguous int8 [M, D], got {q_codes.dtype} "
+                         f"{tuple(q_codes.shape)}")
+    m, d = int(q_codes.shape[0]), int(q_codes.shape[1])
+    _check_embed_dim(d)
+    if d != gallery.dim:
+        raise ValueError(f"queries of width {d}, the gallery holds {gallery.dim}")
+    if not 1 <= m <= GALLERY_MAX_QUERIES:
+        raise ValueError(f"1..{GALLERY_MAX_QUERIES} queries, got {m}")
+    if isinstance(top, bool) or not 1 <= int(top) <= GALLERY_MAX_TOP:
+        raise ValueError(f"top {top!r} outside 1..{GALLERY_MAX_TOP}")
+    if q_codes.device != gallery.device:
+        raise ValueError(f"q_codes on {q_codes.device}, the gallery on {gallery.device}")
+    k, dev = int(top), q_codes.device
+    if out_score is None:
+        out_score = empty(m, k, dtype=torch.float32, device=dev)
+    if out_row is None:
+        out_row = empty(m, k, dtype=torch.int32, device=dev)
+    _check_out("out_score", out_score, torch.float32, (m, k), dev)
+    _check_out("out_row", out_row, torch.int32, (m, k), dev)
+    if q_codes.is_cuda:
+        # the workgroups' partial lists [M, workgroups, top] of (score, row): per call, so that
+        # calls on different streams never share one
+        part = empty(m * int(_native().gallery_workgroups(gallery.capacity)) * k * 2,
+                     dtype=torch.int32, device=dev)
+        _native().gallery_match(q_codes, gallery.codes, gallery.scale, gallery.count, part,
+                                out_score, out_row)
+    else:
+        _ref.gallery_match(q_codes, gallery.codes, gallery.scale, gallery.count, out_score,
+                           out_row)
+    return out_score, out_row
+
+
+# ---------------------------------------------------------------------------
 # camera snapshots: baseline JPEG files of frames that are already on the device
 # ---------------------------------------------------------------------------
 JPEG_SUBSAMPLINGS = _ref.JPEG_SUBSAMPLINGS

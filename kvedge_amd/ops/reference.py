@@ -1346,3 +1346,48 @@ def frame_enhance(images, enh, slot0, out, out_stats):
         d = (((Y2 - Y) * alpha) >> 8).to(torch.int32)
         dst[n] = (rgb + d[..., None]).clamp_(0, 255).to(torch.uint8)
     return dst, out_stats
+
+
+# ---------------------------------------------------------------------------
+# appearance search (csrc/kernels/gallery.hip): int8 embeddings matched to a gallery
+# ---------------------------------------------------------------------------
+def embed_quantize(features, out_codes, out_nrm2):
+    """THE definition of ops.embed_quantize, in integer torch.  ``features`` bf16 [M, H, W, C]:
+    v = float(x), NaN -> 0, t = clamp(v, -16384, 16384), f = rint(t * 256) (an integer, |f| <=
+    2^22), s[c] = the sum of f over the H W positions (|s| <= 2^30), mx = max_c |s[c]|,
+    e = max(0, bitlen(mx) - 7), code[c] = sign(s[c]) min(127, (|s[c]| + (e ? 1 << (e - 1) : 0))
+    >> e), nrm2 = sum_c code[c]^2: average pooling and block-floating-point quantisation with
+    no division, no square root and no float reduction."""
+    v = features.float()
+    v = torch.where(torch.isnan(v), torch.zeros_like(v), v).clamp_(-16384.0, 16384.0)
+    s = (v * 256.0).round_().to(torch.int64).sum(dim=(1, 2))               # [M, C]
+    mx = s.abs().amax(dim=1, keepdim=True)
+    bitlen = (mx >= (1 << torch.arange(31, dtype=torch.int64))).sum(dim=1, keepdim=True)
+    e = (bitlen - 7).clamp_(min=0)
+    rnd = torch.where(e > 0, torch.ones_like(e) << (e - 1).clamp_(min=0), torch.zeros_like(e))
+    code = torch.sign(s) * ((s.abs() + rnd) >> e).clamp_(max=127)
+    out_codes.copy_(code.to(torch.int8))
+    out_nrm2.copy_((code * code).sum(dim=1).to(torch.int32))
+    return out_codes, out_nrm2
+
+
+def gallery_match(q_codes, codes, scale, count, out_score, out_row):
+    """THE definition of ops.gallery_match.  ``q_codes`` int8 [M, D] against ``codes`` int8
+    [cap, D]: row j counts if j < min(count, cap) and scale[j] > 0; its score is
+    float32(dot_int(q, codes[j])) * scale[j], one conversion and one fp32 multiply.  The K =
+    out_score.shape[1] best rows by (score descending, row ascending) -- a stable descending
+    sort -- go to ``out_score`` fp32 [M, K] / ``out_row`` int32 [M, K]; slots past the number
+    of counted rows hold 0 / -1."""
+    K = int(out_score.shape[1])
+    n = max(0, min(int(count.reshape(-1)[0]), int(codes.shape[0])))
+    rows = torch.nonzero(scale[:n] > 0).reshape(-1)
+    out_score.zero_()
+    out_row.fill_(-1)
+    if rows.numel():
+        dot = q_codes.long() @ codes[rows].long().T
+        score = dot.float() * scale[rows].float()[None, :]
+        s, i = torch.sort(score, dim=1, descending=True, stable=True)
+        k = min(K, int(rows.numel()))
+        out_score[:, :k] = s[:, :k]
+        out_row[:, :k] = rows[i[:, :k]].to(torch.int32)
+    return out_score, out_row
