@@ -909,6 +909,44 @@ void track_update(const at::Tensor& det, const at::Tensor& count, at::Tensor& st
   TORCH_CHECK(rc == 0, "kvedge: track_update failed rc=", rc);
 }
 
+// K28: cross-group detection merge (csrc/kernels/det_merge.hip).  det fp32 [groups * N, R, 6] /
+// count int32 [groups * N], group-major; out fp32 [N, max_det, 6] / out_count int32 [N]
+void det_merge(const at::Tensor& det, const at::Tensor& count, at::Tensor& out,
+               at::Tensor& out_count, int64_t groups, int64_t thr_q, bool use_iou,
+               bool class_aware, bool nmm) {
+  check_dev(det, "det");
+  check_dev(count, "count");
+  check_dev(out, "out");
+  check_dev(out_count, "out_count");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6,
+              "kvedge: det fp32 [groups*N,R,6]");
+  const int64_t GN = det.size(0), R = det.size(1);
+  TORCH_CHECK(groups >= 1 && GN % groups == 0, "kvedge: det_merge rows ", GN,
+              " are no multiple of groups ", groups);
+  const int64_t N = GN / groups;
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == GN,
+              "kvedge: count int32 [groups*N]");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 3 && out.size(0) == N &&
+                  out.size(2) == 6, "kvedge: det_merge out fp32 [N,max_det,6]");
+  const int64_t max_det = out.size(1);
+  TORCH_CHECK(out_count.scalar_type() == at::kInt && out_count.dim() == 1 &&
+                  out_count.size(0) == N, "kvedge: det_merge out_count int32 [N]");
+  TORCH_CHECK(R >= 1 && R <= 300 && groups * R <= 4096,
+              "kvedge: det_merge needs R in 1..300 and groups * R <= 4096, got ", groups, " x ", R);
+  TORCH_CHECK(max_det >= 1 && max_det <= R, "kvedge: det_merge max_det is 1..R, got ", max_det);
+  TORCH_CHECK(thr_q >= 1 && thr_q <= 1024, "kvedge: det_merge thr_q is 1..1024");
+  TORCH_CHECK(N <= 65535, "kvedge: det_merge too many cameras");
+  TORCH_CHECK(det.device() == count.device() && det.device() == out.device() &&
+                  det.device() == out_count.device(),
+              "kvedge: det_merge operands on different devices");
+  const c10::DeviceGuard g(det.device());
+  const int rc = kv_det_merge(det.data_ptr<float>(), count.data_ptr<int>(), out.data_ptr<float>(),
+                              out_count.data_ptr<int>(), (int)N, (int)groups, (int)R, (int)max_det,
+                              (int)thr_q, use_iou ? 1 : 0, class_aware ? 1 : 0, nmm ? 1 : 0,
+                              cur_stream(det));
+  TORCH_CHECK(rc == 0, "kvedge: det_merge failed rc=", rc);
+}
+
 // K19: line crossings and zone occupancy (csrc/kernels/zones.hip), after the same step's
 // track_update.  track_state int32 [S, 12 T + 4] (read only), zone_state int32 [S, 4 T + 48],
 // table int32 [S, 188]; batch row n of det / count is stream slot0 + n
@@ -1446,6 +1484,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("roi_crop_nv12_band(Tensor src, Tensor det, Tensor count, Tensor(a!) dst, int pad, int band) -> ()");
   m.def("track_update(Tensor det, Tensor count, Tensor(a!) state, Tensor(b!) track_id, int slot0, "
         "int thr_q, int max_age, int min_hits, bool class_aware) -> ()");
+  m.def("det_merge(Tensor det, Tensor count, Tensor(a!) out, Tensor(b!) out_count, int groups, "
+        "int thr_q, bool use_iou, bool class_aware, bool nmm) -> ()");
   m.def("zone_update(Tensor det, Tensor count, Tensor track_state, Tensor(a!) zone_state, "
         "Tensor table, Tensor(b!) zone_mask, Tensor(c!) zone_counts, int slot0) -> ()");
   m.def("frame_watch(Tensor src, Tensor(a!) state, Tensor(b!) stats, Tensor(c!) mask, int slot0, "
@@ -1510,6 +1550,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("roi_crop_nv12", roi_crop_nv12);
   m.impl("roi_crop_nv12_band", roi_crop_nv12_band);
   m.impl("track_update", track_update);
+  m.impl("det_merge", det_merge);
   m.impl("zone_update", zone_update);
   m.impl("frame_watch", frame_watch);
   m.impl("frame_enhance", frame_enhance);

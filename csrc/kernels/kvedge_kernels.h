@@ -336,6 +336,17 @@ int kv_gallery_workgroups(int cap);
 int kv_gallery_match(const signed char* q, const signed char* codes, const float* scale,
                      const int* count, void* part, long long part_bytes, float* score, int* row,
                      int M, int D, int cap, int K, hipStream_t s);
+// K28 (det_merge.hip): the NMS outputs of `groups` passes over each of N cameras merged into one
+// list per camera, one launch, one workgroup per camera, bit-identical to
+// ops.reference.det_merge (the rule is at the top of det_merge.hip).  det fp32 [groups * N, R, 6]
+// / count int32 [groups * N], group-major (row g * N + n), all boxes in one pixel frame; out
+// fp32 [N, max_det, 6] / out_count int32 [N], every element written.  thr_q = floor(thr * 1024
+// + 0.5); use_iou: denominator union, else min(area); nmm: kept boxes grow to the hull of what
+// they absorbed.  Returns -1 R outside 1..300 or groups * R outside 1..4096, -2 max_det outside
+// 1..R, -3 thr_q outside 1..1024, -4 N outside 0..65535, -7 misaligned operand.
+int kv_det_merge(const float* det, const int* count, float* out, int* out_count, int N,
+                 int groups, int R, int max_det, int thr_q, int use_iou, int class_aware, int nmm,
+                 hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

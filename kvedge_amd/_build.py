@@ -101,8 +101,12 @@ if os.environ.get("KVEDGE_VARIANT"):
 # on does not let the compiler choose them.  A guard, not a fix: this kernel is all integer
 # (six int -> float conversions per det row) and its code has no v_pk_* with or without the
 # flag.  -Xclang reaches the host pass too, which reports the feature as unknown and ignores it.
+# det_merge.hip: integer too; its float work is the quantisation q(x) = floor(x * 4 + 0.5) of
+# four edges per row and the hull's q * 0.25f on the way out, two values per store, which must
+# stay bit-exact against the CPU reference.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"motion_blobs.hip": NO_PACKED_FP32, "gallery.hip": NO_PACKED_FP32}
+EXTRA = {"motion_blobs.hip": NO_PACKED_FP32, "gallery.hip": NO_PACKED_FP32,
+         "det_merge.hip": NO_PACKED_FP32}
 
 
 def build(force: bool = False, jobs: int = 0, verbose: bool = False, asan: bool = False) -> str:

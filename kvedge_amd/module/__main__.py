@@ -187,6 +187,13 @@ def main(argv=None):
                          "gains `matches`; direct methods gallery_enrol / gallery_remove)")
     ap.add_argument("--gallery-top", type=int, default=d.gallery_top)
     ap.add_argument("--gallery-threshold", type=float, default=d.gallery_threshold)
+    ap.add_argument("--slice-grid", default=d.slice_grid,
+                    help="--model yolov8n with a frame size: also detect on COLSxROWS overlapping "
+                         "tiles of the native frame (up to 4x4) and merge the boxes on the device "
+                         "(twin keys `slice_grid`, `slice_overlap`, `slice_full`, `slice_mode`, "
+                         "`slice_metric`, `slice_thr`)")
+    ap.add_argument("--slice-overlap", type=float, default=d.slice_overlap,
+                    help="share of a tile that neighbouring tiles have in common (0..0.5)")
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
@@ -249,6 +256,7 @@ def main(argv=None):
                        snapshot_privacy_zones=a.privacy_zones_json,
                        gallery=a.gallery, gallery_top=a.gallery_top,
                        gallery_threshold=a.gallery_threshold,
+                       slice_grid=a.slice_grid, slice_overlap=a.slice_overlap,
                        enhance=bool(a.enhance),
                        enhance_mode=a.enhance or d.enhance_mode).validate()
     # one IoT Edge identity per VM: only local rank 0 talks to edgeHub

@@ -443,6 +443,13 @@ class ModuleApp:
                     self.cascade, self.match_totals = self.model, MatchTotals()
                 else:
                     self.model = KvDetectClassify(self.model, clf, cfg.crops_per_image)
+            if cfg.slice_grid:  # under the tracker: it tracks the merged boxes
+                from ..models.slicing import KvSliced
+
+                self.model = KvSliced(self.model, cfg.batch, grid=cfg.slice_dims(),
+                                      overlap=cfg.slice_overlap, full=cfg.slice_full,
+                                      mode=cfg.slice_mode, metric=cfg.slice_metric,
+                                      thr=cfg.slice_thr)
             if cfg.track:
                 from ..models.tracking import KvTracked
 

@@ -259,6 +259,18 @@ class ModuleConfig:
     gallery: str = ""
     gallery_top: int = 1
     gallery_threshold: float = 0.5
+    # sliced detection (models.slicing.KvSliced, model "yolov8n" with a frame size): slice_grid
+    # "" = off, "COLSxROWS" up to 4x4 = also detect on that grid of overlapping tiles of the
+    # native frame (neighbours share slice_overlap, 0..0.5, of a tile) and, with slice_full,
+    # on the whole frame; the groups' boxes are merged on the device (ops.det_merge) by
+    # slice_mode "nmm" (absorbed boxes grow the kept one) or "nms", slice_metric "ios" (overlap
+    # over the smaller box) or "iou", at slice_thr.  Every key needs a rebuild
+    slice_grid: str = ""
+    slice_overlap: float = 0.2
+    slice_full: bool = True
+    slice_mode: str = "nmm"
+    slice_metric: str = "ios"
+    slice_thr: float = 0.5
     native_loop: bool = True   # GPU: replay the graph from the C++ serve loop
     steps_per_poll: int = 1      # graph replays per module step (native loop)
     # seconds of in-graph tile refinement when the engine is built (engine.prepare refine_s;
@@ -282,7 +294,8 @@ class ModuleConfig:
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
                "watch_bg_shift", "watch_regions", "watch_region_max",
                "watch_region_connectivity", "snapshots", "snapshot_width", "snapshot_subsampling",
-               "snapshot_annotate", "enhance", "gallery", "gallery_top")
+               "snapshot_annotate", "enhance", "gallery", "gallery_top", "slice_grid",
+               "slice_overlap", "slice_full", "slice_mode", "slice_metric", "slice_thr")
 
     def __post_init__(self):
         for kind in ("lines", "zones"):  # lists as given (or JSON text) -> normal form
@@ -485,6 +498,35 @@ class ModuleConfig:
             raise ValueError("gallery_threshold must be -1..1")
         if self.gallery and self.model != "detect-classify":
             raise ValueError("gallery needs crops to embed: model detect-classify")
+        # sliced detection (models.slicing.KvSliced / ops.det_merge)
+        if not 0.0 <= self.slice_overlap <= 0.5:
+            raise ValueError("slice_overlap must be 0..0.5")
+        if self.slice_mode not in ("nmm", "nms"):
+            raise ValueError(f"slice_mode must be nmm or nms, got {self.slice_mode!r}")
+        if self.slice_metric not in ("ios", "iou"):
+            raise ValueError(f"slice_metric must be ios or iou, got {self.slice_metric!r}")
+        if not 1.0 / 1024 <= self.slice_thr <= 1.0:
+            raise ValueError("slice_thr must be in (0, 1]")
+        if self.slice_grid:  # cross-key limits bind only when slicing is on
+            groups = self.slice_tiles() + int(self.slice_full)
+            if self.model != "yolov8n":
+                raise ValueError(f"slice_grid needs model yolov8n, got {self.model} (the "
+                                 "detect-classify cascade is not sliced)")
+            if not self.frame_height:
+                raise ValueError("slice_grid cuts tiles from native frames: it needs "
+                                 "frame_height and frame_width")
+            if self.views:
+                raise ValueError("slice_grid cuts its own tile views: it cannot be combined "
+                                 "with views")
+            if self.enhance:
+                raise ValueError("slice_grid cannot be combined with enhance")
+            if self.batch * groups > 4096:
+                raise ValueError("batch * (tiles + slice_full) must be <= 4096")
+            if groups * self.max_det > 4096:
+                raise ValueError("(tiles + slice_full) * max_det must be <= 4096")
+            if self.frame_height < 2 * self.slice_dims()[1] or (
+                    self.frame_width < 2 * self.slice_dims()[0]):
+                raise ValueError("the frame is too small for slice_grid")
         if not 1 <= self.steps_per_poll <= 1000:
             raise ValueError("steps_per_poll must be 1..1000")
         if not 0.0 <= self.refine_s <= 600.0:
@@ -578,6 +620,22 @@ class ModuleConfig:
 
     GALLERY_KEYS = ("gallery", "gallery_top", "gallery_threshold")
 
+    SLICE_KEYS = ("slice_grid", "slice_overlap", "slice_full", "slice_mode", "slice_metric",
+                  "slice_thr")
+
+    def slice_dims(self):
+        """(cols, rows) of ``slice_grid`` ("2x2"; 1..4 each), or None when slicing is off."""
+        if not self.slice_grid:
+            return None
+        parts = self.slice_grid.lower().split("x")
+        if len(parts) != 2 or not all(p.isdigit() and 1 <= int(p) <= 4 for p in parts):
+            raise ValueError(f"slice_grid is COLSxROWS with 1..4 each, got {self.slice_grid!r}")
+        return int(parts[0]), int(parts[1])
+
+    def slice_tiles(self) -> int:
+        dims = self.slice_dims()
+        return dims[0] * dims[1] if dims else 0
+
     SNAPSHOT_KEYS = ("snapshots", "snapshot_width", "snapshot_subsampling", "snapshot_quality",
                      "snapshot_every_s", "snapshot_max_bytes")
 
@@ -649,5 +707,9 @@ class ModuleConfig:
         # and the appearance-search keys
         if all(getattr(self, k) == getattr(base, k) for k in self.GALLERY_KEYS):
             for k in self.GALLERY_KEYS:
+                d.pop(k)
+        # and the sliced-detection keys
+        if all(getattr(self, k) == getattr(base, k) for k in self.SLICE_KEYS):
+            for k in self.SLICE_KEYS:
                 d.pop(k)
         return d

@@ -1352,6 +1352,142 @@ def track_update(det: torch.Tensor, count: torch.Tensor, state: TrackState, slot
 
 
 # ---------------------------------------------------------------------------
+# sliced detection: tile views of a frame, and the merge of what the tiles saw
+# ---------------------------------------------------------------------------
+MERGE_MAX_CANDIDATES = 4096  # groups * R: what one workgroup sorts in LDS
+MERGE_MODES = ("nmm", "nms")
+MERGE_METRICS = ("ios", "iou")
+SLICE_MAX_GRID = 4
+
+
+def det_merge(det: torch.Tensor, count: torch.Tensor, groups: int, *, mode: str = "nmm",
+              metric: str = "ios", thr: float = 0.5, class_aware: bool = True,
+              max_det: Optional[int] = None, out: Optional[torch.Tensor] = None,
+              out_count: Optional[torch.Tensor] = None):
+    """Merge ``groups`` :func:`nms` outputs per camera -- the tiles of a sliced frame and the
+    full frame -- into one list: ``det`` fp32 [groups * N, R, 6] / ``count`` int32 [groups * N],
+    group-major (row g * N + n is group g of camera n), all boxes already in one pixel frame
+    -> (det fp32 [N, max_det, 6], count int32 [N]); ``max_det`` defaults to R.  Candidates go
+    by score (then group, then row); one that matches an earlier kept one -- same class
+    (``class_aware``), overlap over the union (``metric="iou"``) or over the smaller box
+    ("ios", which lets a whole box absorb the half a tile border cut off) of at least ``thr``
+    -- is absorbed by the earliest such one; ``mode="nms"`` keeps the kept rows as they are,
+    "nmm" grows each kept box to the hull of what it absorbed.  The sweep ends at ``max_det``
+    kept rows; rows past the new count are zero.  Integer arithmetic on quarter-pixel boxes, the
+    tracker's: the rule is written out in ops.reference.det_merge, which the GPU
+    (csrc/kernels/det_merge.hip) equals bit for bit.  ``1 <= max_det <= R <= TRACK_MAX_DET``
+    and ``groups * R <= MERGE_MAX_CANDIDATES``: nothing is truncated silently."""
+    if mode not in MERGE_MODES:
+        raise ValueError(f"mode must be one of {MERGE_MODES}, got {mode!r}")
+    if metric not in MERGE_METRICS:
+        raise ValueError(f"metric must be one of {MERGE_METRICS}, got {metric!r}")
+    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 6:
+        raise ValueError(f"det must be fp32 [groups * N, R, 6], got {det.dtype} {tuple(det.shape)}")
+    if isinstance(groups, bool) or int(groups) < 1 or det.shape[0] % int(groups):
+        raise ValueError(f"det has {det.shape[0]} rows, no multiple of groups = {groups!r}")
+    groups = int(groups)
+    gn, r = int(det.shape[0]), int(det.shape[1])
+    n = gn // groups
+    if count.dtype != torch.int32 or tuple(count.shape) != (gn,):
+        raise ValueError(f"count must be int32 [{gn}], got {count.dtype} {tuple(count.shape)}")
+    if not det.is_contiguous() or not count.is_contiguous():
+        raise ValueError("det and count must be contiguous")
+    if count.device != det.device:
+        raise ValueError(f"det on {det.device}, count on {count.device}")
+    if not 1 <= r <= TRACK_MAX_DET or groups * r > MERGE_MAX_CANDIDATES:
+        raise ValueError(f"det_merge needs 1 <= R <= {TRACK_MAX_DET} and groups * R <= "
+                         f"{MERGE_MAX_CANDIDATES}, got {groups} x {r}")
+    max_det = r if max_det is None else int(max_det)
+    if not 1 <= max_det <= r:
+        raise ValueError(f"det_merge needs 1 <= max_det <= R = {r}, got {max_det}")
+    thr_q = track_thr_q(thr)
+    if not 1 <= thr_q <= 1024:
+        raise ValueError(f"thr {thr} gives a threshold of {thr_q}/1024, outside 1..1024")
+    if out is None:
+        out = empty(n, max_det, 6, dtype=torch.float32, device=det.device)
+    if out_count is None:
+        out_count = empty(n, dtype=torch.int32, device=det.device)
+    if (out.dtype != torch.float32 or tuple(out.shape) != (n, max_det, 6)
+            or not out.is_contiguous() or out.device != det.device):
+        raise ValueError(f"out must be contiguous fp32 [{n}, {max_det}, 6] on {det.device}")
+    if (out_count.dtype != torch.int32 or tuple(out_count.shape) != (n,)
+            or not out_count.is_contiguous() or out_count.device != det.device):
+        raise ValueError(f"out_count must be contiguous int32 [{n}] on {det.device}")
+    args = (groups, thr_q, metric == "iou", bool(class_aware), mode == "nmm")
+    if det.is_cuda:
+        _native().det_merge(det, count, out, out_count, *args)
+    else:
+        _ref.det_merge(det, count, *args, out, out_count)
+    return out, out_count
+
+
+def _slice_axis(size: int, k: int, overlap: float):
+    import math
+
+    se = size - (size & 1)
+    w = -(-se // k)
+    w = min(se, w + (w & 1))
+    while k > 1:
+        step = 2 * -(-(se - w) // (2 * (k - 1)))  # the largest even step between origins
+        if step <= w - math.floor(overlap * w):
+            break
+        w += 2
+    return w, [2 * ((i * (se - w)) // (2 * (k - 1))) if k > 1 else 0 for i in range(k)]
+
+
+def check_slice_grid(grid, overlap):
+    """(cols, rows, overlap) of a tile grid, or ValueError: 1..SLICE_MAX_GRID tiles per axis,
+    neighbours sharing 0..0.5 of a tile."""
+    try:
+        cols, rows = (int(v) for v in grid)
+        overlap = float(overlap)
+    except (TypeError, ValueError):
+        raise ValueError(f"grid is (cols, rows) and overlap a number, got {grid!r}, "
+                         f"{overlap!r}") from None
+    if not (1 <= cols <= SLICE_MAX_GRID and 1 <= rows <= SLICE_MAX_GRID):
+        raise ValueError(f"grid {cols}x{rows} outside 1..{SLICE_MAX_GRID} per axis")
+    if not 0.0 <= overlap <= 0.5:
+        raise ValueError(f"overlap {overlap} outside 0..0.5")
+    return cols, rows, overlap
+
+
+def slice_rois(src_hw, grid=(2, 2), overlap: float = 0.2):
+    """The ``cols * rows`` tiles of a ``grid`` = (cols, rows) over a frame of ``src_hw`` =
+    (Hs, Ws), row-major, as integer ROIs (x0, y0, w, h).  The rule, per axis of S pixels (an odd
+    S loses its last pixel) with k tiles: w is the smallest even size, from ceil(S / k) up, whose
+    largest step between origins, 2 * ceil((S - w) / (2 (k - 1))), still leaves neighbours
+    floor(overlap * w) shared pixels; origin i is (i * (S - w) / (k - 1)) rounded down to even.
+    So all tiles have one even size and even origins (NV12), the first and last are flush with
+    the frame, neighbours share at least floor(overlap * w) pixels, and k = 1 is the frame."""
+    cols, rows, overlap = check_slice_grid(grid, overlap)
+    try:
+        hs, ws = (int(v) for v in src_hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"src_hw is (Hs, Ws), got {src_hw!r}") from None
+    if hs < 2 * rows or ws < 2 * cols:
+        raise ValueError(f"a frame of {hs}x{ws} is too small for a {cols}x{rows} grid")
+    w, xs = _slice_axis(ws, cols, overlap)
+    h, ys = _slice_axis(hs, rows, overlap)
+    return [(x, y, w, h) for y in ys for x in xs]
+
+
+def slice_views(streams: int, src_hw, dst_hw, grid=(2, 2), overlap: float = 0.2,
+                device="cpu") -> CameraViews:
+    """The tile views of ``streams`` cameras as one :class:`CameraViews` of
+    ``cols * rows * streams`` slots: slot ``g * streams + n`` is tile g (:func:`slice_rois`) of
+    camera n, letterboxed into ``dst_hw``.  ``frame_warp(src[lo:hi], views, out=...,
+    slot0=g * streams + lo)`` fills tile g of a slice, and :func:`view_to_source` with the same
+    slot maps its boxes back to frame pixels."""
+    rois, s = slice_rois(src_hw, grid, overlap), int(streams)
+    views = CameraViews(len(rois) * s, src_hw, dst_hw, device=device)
+    for g, (x, y, w, h) in enumerate(rois):
+        mesh, pad = view_mesh_from(views.src_hw, views.dst_hw, {"roi": [x, y, x + w, y + h]})
+        views.mesh[g * s:(g + 1) * s] = torch.from_numpy(mesh).to(views.device)
+        views.pad[g * s:(g + 1) * s] = pad
+    return views
+
+
+# ---------------------------------------------------------------------------
 # lines and zones: stable ids -> crossings, occupancy, dwell
 # ---------------------------------------------------------------------------
 ZONE_MAX_LINES = 8

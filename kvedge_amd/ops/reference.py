@@ -452,6 +452,63 @@ def track_update(det, count, state, slot0, thr_q, max_age, min_hits, class_aware
     return out
 
 
+def det_merge(det, count, groups, thr_q, use_iou, class_aware, nmm, out, out_count):
+    """Several NMS outputs per camera -> one list: THE definition the HIP kernel
+    (csrc/kernels/det_merge.hip) equals bit for bit.  det fp32 [groups * N, R, 6] / count int32
+    [groups * N], group-major (row g * N + n is group g of camera n), all boxes in one pixel
+    frame; out fp32 [N, max_det, 6] / out_count int32 [N].  Per camera:
+
+    1. candidates: rows r < clamp(count, 0, R) of every group; box = ``track_quantize``, class
+       = ``track_class``, score s = score if score > 0 else +0 (NaN and negatives are 0);
+    2. order: s descending, then group ascending, then row ascending;
+    3. match(a, b): equal classes (``class_aware``), inter > 0 and inter * 1024 >= thr_q * denom
+       (integers), denom = union (``use_iou``) or min(area_a, area_b); always on the original
+       quantised boxes, never on a grown one;
+    4. sweep in order, until max_det are kept: a candidate matching an earlier kept one is
+       absorbed by the earliest such one, else it is kept; what follows the last kept one is
+       dropped, not absorbed;
+    5. row k: the kept candidate's own six values with the score as s; ``nmm``: the box is the
+       hull of the kept box and all it absorbed, q / 4.  Rows >= out_count[n] are zero."""
+    GN, R, _ = det.shape
+    N, max_det = GN // groups, out.shape[1]
+    out.zero_()
+    for n in range(N):
+        cand = torch.cat([det[g * N + n, :min(max(int(count[g * N + n]), 0), R)]
+                          for g in range(groups)])
+        q, cls = track_quantize(cand[:, :4]), track_class(cand[:, 5])
+        s = torch.where(cand[:, 4] > 0, cand[:, 4], torch.zeros(()))
+        area = _box_area(q)
+        kept, hulls = [], []
+        for i in torch.sort(s, descending=True, stable=True).indices.tolist():
+            if len(kept) == max_det:
+                break
+            if kept:
+                k = q[kept]
+                iw = (torch.minimum(k[:, 2], q[i, 2]) - torch.maximum(k[:, 0], q[i, 0])).clamp_min(0)
+                ih = (torch.minimum(k[:, 3], q[i, 3]) - torch.maximum(k[:, 1], q[i, 1])).clamp_min(0)
+                inter = iw * ih
+                ka = area[kept]
+                denom = ka + area[i] - inter if use_iou else torch.minimum(ka, area[i])
+                m = (inter > 0) & (inter * 1024 >= thr_q * denom)
+                if class_aware:
+                    m &= cls[kept] == cls[i]
+                if bool(m.any()):
+                    h = hulls[int(m.nonzero()[0, 0])]
+                    h[:2] = torch.minimum(h[:2], q[i, :2])
+                    h[2:] = torch.maximum(h[2:], q[i, 2:])
+                    continue
+            kept.append(i)
+            hulls.append(q[i].clone())
+        nk = len(kept)
+        out_count[n] = nk
+        if nk:
+            out[n, :nk] = cand[kept]
+            out[n, :nk, 4] = s[kept]
+            if nmm:
+                out[n, :nk, :4] = torch.stack(hulls).float() / 4.0
+    return out, out_count
+
+
 ZONE_MAX = 8  # lines, zones and vertices per zone, per camera
 
 
