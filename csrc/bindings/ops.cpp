@@ -1167,6 +1167,54 @@ void jpeg_encode(const at::Tensor& images, const at::Tensor& qtab, const at::Ten
   TORCH_CHECK(rc == 0, "kvedge: jpeg_encode failed rc=", rc);
 }
 
+// K29: baseline JPEG decoder (csrc/kernels/jpeg_decode.hip).  files uint8 [N,row_bytes], one
+// file per row; tables / mpos / planes are the workspaces of an ops.JpegDecoder made for
+// (H, W) and row_bytes; out uint8 [N,H,W,3], status int32 [N].  Everything is validated before
+// the first launch.
+void jpeg_decode(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
+                 at::Tensor& planes, at::Tensor& out, at::Tensor& status, int64_t lanes) {
+  check_dev(files, "files");
+  check_dev(tables, "tables");
+  check_dev(mpos, "mpos");
+  check_dev(planes, "planes");
+  check_dev(out, "out");
+  check_dev(status, "status");
+  TORCH_CHECK(files.scalar_type() == at::kByte && files.dim() == 2 && files.is_contiguous() &&
+                  files.size(1) >= 16 && files.size(1) % 16 == 0 &&
+                  files.size(1) <= 0x7ffffff0ll,
+              "kvedge: jpeg_decode files uint8 [N, row_bytes] contiguous, row_bytes % 16 == 0");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(3) == 3 &&
+                  out.is_contiguous() && out.size(0) == files.size(0),
+              "kvedge: jpeg_decode out uint8 [N,H,W,3] contiguous");
+  const int64_t N = files.size(0), H = out.size(1), W = out.size(2);
+  TORCH_CHECK(H >= 1 && H <= 8192 && W >= 1 && W <= 8192,
+              "kvedge: jpeg_decode image size 1..8192, got ", H, "x", W);
+  TORCH_CHECK(N <= 65535, "kvedge: jpeg_decode too many files");
+  TORCH_CHECK(lanes == 16 || lanes == 32 || lanes == 64, "kvedge: jpeg_decode lanes 16/32/64");
+  const int64_t max_int = ((H + 7) / 8) * ((W + 7) / 8);
+  const int64_t plane = ((H + 15) / 16 * 16) * ((W + 15) / 16 * 16);
+  TORCH_CHECK(tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() >= N * kv_jpeg_decode_table_bytes(),
+              "kvedge: jpeg_decode tables uint8 [N,", kv_jpeg_decode_table_bytes(), "]");
+  TORCH_CHECK(mpos.scalar_type() == at::kInt && mpos.is_contiguous() &&
+                  mpos.numel() >= N * max_int, "kvedge: jpeg_decode mpos int32 [N,", max_int, "]");
+  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.is_contiguous() &&
+                  planes.numel() >= N * 3 * plane,
+              "kvedge: jpeg_decode planes uint8 [N,3,", plane, "]");
+  TORCH_CHECK(status.scalar_type() == at::kInt && status.dim() == 1 && status.is_contiguous() &&
+                  status.size(0) >= N, "kvedge: jpeg_decode status int32 [>= N]");
+  for (const at::Tensor* t :
+       std::initializer_list<const at::Tensor*>{&tables, &mpos, &planes, &out, &status})
+    TORCH_CHECK(t->device() == files.device(), "kvedge: jpeg_decode operands on different devices");
+  const c10::DeviceGuard g(files.device());
+  const int rc = kv_jpeg_decode(files.data_ptr<uint8_t>(), tables.data_ptr<uint8_t>(),
+                                mpos.data_ptr<int>(), planes.data_ptr<uint8_t>(),
+                                out.data_ptr<uint8_t>(), status.data_ptr<int>(), (int)N,
+                                (long long)files.size(1), (int)H, (int)W, (int)lanes,
+                                cur_stream(files));
+  TORCH_CHECK(rc == 0, "kvedge: jpeg_decode failed rc=", rc);
+}
+
 // K22: snapshot annotation (csrc/kernels/annotate.hip).  images uint8 [N,H,W,3], drawn in
 // place; table int32 [S,168] and font int32 [88] belong to an ops.AnnotateStyle; det / count /
 // track_id are optional (no det: only the privacy polygons); batch row n is camera slot0 + n.
@@ -1495,6 +1543,8 @@ TORCH_LIBRARY(kvedge, m) {
   m.def("jpeg_encode(Tensor images, Tensor qtab, Tensor huff, Tensor header, Tensor(a!) coef, "
         "Tensor(b!) scratch, Tensor(c!) seglen, Tensor(d!) out, Tensor(e!) length, bool sub420) "
         "-> ()");
+  m.def("jpeg_decode(Tensor files, Tensor(a!) tables, Tensor(b!) mpos, Tensor(c!) planes, "
+        "Tensor(d!) out, Tensor(e!) status, int lanes) -> ()");
   m.def("annotate(Tensor(a!) images, Tensor table, Tensor font, Tensor? det, Tensor? count, "
         "Tensor? track_id, int Hs, int Ws, int slot0) -> ()");
   m.def("motion_blobs(Tensor mask, Tensor params, Tensor ignore, Tensor(a!) det, Tensor(b!) count, "
@@ -1555,6 +1605,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("frame_watch", frame_watch);
   m.impl("frame_enhance", frame_enhance);
   m.impl("jpeg_encode", jpeg_encode);
+  m.impl("jpeg_decode", jpeg_decode);
   m.impl("annotate", annotate);
   m.impl("motion_blobs", motion_blobs);
   m.impl("embed_quantize", embed_quantize);

@@ -347,6 +347,19 @@ int kv_gallery_match(const signed char* q, const signed char* codes, const float
 int kv_det_merge(const float* det, const int* count, float* out, int* out_count, int N,
                  int groups, int R, int max_det, int thr_q, int use_iou, int class_aware, int nmm,
                  hipStream_t s);
+// K29 (jpeg_decode.hip): baseline JPEG files -> uint8 RGB [N,H,W,3] and status int32 [N], three
+// launches, byte-identical to ops.reference.jpeg_decode (status words and malformed files
+// included; the rules are in jpeg_decode_core.h).  files uint8 [N,row_bytes] (row_bytes % 16 ==
+// 0, 16-byte aligned), one file per row from SOI.  Scratch: tables uint8
+// [N,kv_jpeg_decode_table_bytes()] (16-byte aligned), mpos int32 [N, ceil(H/8) * ceil(W/8)],
+// planes uint8 [N,3,H16,W16] (H16 / W16 = H / W rounded up to 16; 16-byte aligned).  lanes =
+// restart intervals per wave of the decode launch: 16, 32 or 64.  status[n] = 0 or -(error
+// bits).  Returns -1 H or W outside 1..8192, -2 N outside 0..65535, -3 row_bytes, -5 lanes,
+// -7 misaligned operand.  N == 0 launches nothing.
+int kv_jpeg_decode_table_bytes(void);
+int kv_jpeg_decode(const unsigned char* files, unsigned char* tables, int* mpos,
+                   unsigned char* planes, unsigned char* out, int* status, int N,
+                   long long row_bytes, int H, int W, int lanes, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

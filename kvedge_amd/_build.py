@@ -5,7 +5,8 @@ Builds, with hipcc and no hipify step:
     TORCH_LIBRARY bindings in ``csrc/bindings`` (loaded via torch.ops.load_library);
   * ``kvedge_amd/bin/kv_rccl_bench`` -- native RCCL all-reduce/broadcast bandwidth
     bench (SURVEY.md §2.6 C5);
-  * ``kvedge_amd/bin/kv_runtime_selftest`` -- host self-test of the native runtime.
+  * ``kvedge_amd/bin/kv_runtime_selftest`` -- host self-test of the native runtime;
+  * ``kvedge_amd/bin/kv_jpeg_decode_selftest`` -- the JPEG decoder core over files on the CPU.
 
 The .so links against the HIP runtime that torch already loaded (same soname
 ``libamdhip64.so.7``), so there is exactly one HIP runtime per process.
@@ -161,6 +162,8 @@ def build(force: bool = False, jobs: int = 0, verbose: bool = False, asan: bool 
         "kv_rccl_bench": (os.path.join(CSRC, "comm", "rccl_bench.cpp"),
                           ["-lrccl"]),
         "kv_runtime_selftest": (os.path.join(CSRC, "runtime", "selftest_main.cpp"), []),
+        "kv_jpeg_decode_selftest": (os.path.join(CSRC, "runtime",
+                                                 "jpeg_decode_selftest_main.cpp"), []),
     }
     for name, (src, libs) in tools.items():
         if not os.path.exists(src):
@@ -186,6 +189,15 @@ def build_asan() -> str:
     _run([hipcc(), "-O1", "-g", "-std=c++17", f"--offload-arch={ARCH}",
           "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
           "-Xarch_host", "-fno-omit-frame-pointer", f"-I{CSRC}/runtime", *srcs, "-o", out,
+          f"-L{ROCM}/lib", f"-Wl,-rpath,{ROCM}/lib"])
+    # the JPEG decoder core (csrc/kernels/jpeg_decode_core.h) over files on the CPU: host code
+    # only, run by tools/jpeg_decode_hostcheck.py
+    _run([hipcc(), "-O1", "-g", "-std=c++17", f"--offload-arch={ARCH}",
+          "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
+          "-Xarch_host", "-fno-sanitize-recover=undefined",
+          "-Xarch_host", "-fno-omit-frame-pointer", f"-I{CSRC}/kernels",
+          os.path.join(CSRC, "runtime", "jpeg_decode_selftest_main.cpp"),
+          "-o", os.path.join(BIN, "kv_jpeg_decode_selftest_asan"),
           f"-L{ROCM}/lib", f"-Wl,-rpath,{ROCM}/lib"])
     return out
 

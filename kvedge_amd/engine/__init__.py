@@ -64,6 +64,9 @@ def _cat_outputs(parts):
     return tuple(torch.cat(xs, 0) for xs in zip(*parts))
 
 
+FRAME_CODECS = ("raw", "jpeg")
+
+
 class InferenceEngine:
     """Runs ``model(frames_u8) -> outputs`` on static-shape batches.
 
@@ -80,6 +83,13 @@ class InferenceEngine:
     decoders deliver them, ``source_frames`` is [B, Hs * 3 // 2, Ws] (half the bytes through
     the ring and over PCIe) and the resample converts each source tap to RGB on the way
     (ops.frame_resize(..., src_format="nv12")).  NV12 needs ``frame_hw``.
+    frame_codec: "raw", or "jpeg": every camera delivers Motion-JPEG.  The input buffer is then
+    ``jpeg_files`` uint8 [B, jpeg_row_bytes] (one baseline JPEG file per row, a tenth of the raw
+    frame through the ring and over PCIe) and the first op of every step decodes it on the device
+    into ``source_frames`` (ops.jpeg_decode), which everything downstream reads unchanged;
+    ``decode_status`` int32 [B] is 0 or minus the error bits of each row's file.  Needs
+    ``frame_hw``, fed frames (synthetic=False) and frame_format "rgb", which is what the decoder
+    produces.  jpeg_row_bytes: bytes per row, a multiple of 16; default ops.jpeg_row_bytes.
     views: an ops.CameraViews with one view per batch row (ROI, rotation, lens dewarp,
     perspective): the front end is then ops.frame_warp in place of the resize, and the boxes go
     back to frame pixels through the same meshes (ops.view_to_source), so everything after the
@@ -104,7 +114,21 @@ class InferenceEngine:
                  seed: int = 0, use_graph: bool = True, synthetic: bool = True,
                  streams: int = 1, frame_hw: Optional[Tuple[int, int]] = None,
                  frame_format: str = "rgb", views: Optional["ops.CameraViews"] = None,
-                 enhance: Optional["ops.FrameEnhance"] = None):
+                 enhance: Optional["ops.FrameEnhance"] = None, frame_codec: str = "raw",
+                 jpeg_row_bytes: Optional[int] = None):
+        if frame_codec not in FRAME_CODECS:
+            raise ValueError(f"frame_codec must be one of {FRAME_CODECS}, got {frame_codec!r}")
+        if frame_codec == "jpeg":
+            if frame_hw is None:
+                raise ValueError("frame_codec='jpeg' needs the size of the incoming frames "
+                                 "(frame_hw)")
+            if frame_format != "rgb":
+                raise ValueError("frame_codec='jpeg' decodes to RGB: it does not combine with "
+                                 f"frame_format={frame_format!r}")
+            if synthetic:
+                raise ValueError("frame_codec='jpeg' needs fed frames (synthetic=False): the "
+                                 "synthetic generator writes pixels, not files")
+        self.frame_codec = frame_codec
         if frame_format not in ops.SRC_FORMATS:
             raise ValueError(f"frame_format must be one of {ops.SRC_FORMATS}, "
                              f"got {frame_format!r}")
@@ -140,6 +164,13 @@ class InferenceEngine:
             self.frame_plan = model.frame_plan(self.frame_hw, image_size)
             shape = (batch, hs * 3 // 2, ws) if nv12 else (batch, hs, ws, 3)
             self.source_frames = torch.empty(*shape, dtype=torch.uint8, device=self.device)
+        # Motion-JPEG input: the fed buffer holds files, decoded into source_frames every step
+        self.jpeg = self.jpeg_files = self.decode_status = None
+        if frame_codec == "jpeg":
+            self.jpeg = ops.JpegDecoder(batch, self.frame_hw, jpeg_row_bytes, device=self.device)
+            self.jpeg_files = torch.zeros(batch, self.jpeg.row_bytes, dtype=torch.uint8,
+                                          device=self.device)
+            self.decode_status = self.jpeg.status
         self.views = views
         if views is not None:
             if not isinstance(views, ops.CameraViews):
@@ -183,7 +214,10 @@ class InferenceEngine:
     @property
     def input_frames(self) -> torch.Tensor:
         """The buffer frames are fed into (ring DMA, set_frames, the synthetic generator):
-        ``source_frames`` with a frame size configured, else the model-size ``frames``."""
+        ``jpeg_files`` for Motion-JPEG input, else ``source_frames`` with a frame size
+        configured, else the model-size ``frames``."""
+        if self.jpeg_files is not None:
+            return self.jpeg_files
         return self.frames if self.source_frames is None else self.source_frames
 
     # one full edge-module step: synthesize frames, run the model
@@ -206,6 +240,9 @@ class InferenceEngine:
         # before NV12 keep their call signatures
         fmt = {} if self.frame_format == "rgb" else {"src_format": self.frame_format}
         plan = self.frame_plan
+        if self.jpeg is not None:
+            ops.jpeg_decode(self.jpeg_files[lo:hi], self.jpeg, out=self.source_frames[lo:hi],
+                            slot0=lo)
         if self.views is None:
             ops.frame_resize(self.source_frames[lo:hi], plan, out=frames, **fmt)
         else:

@@ -197,9 +197,12 @@ def main(argv=None):
     ap.add_argument("--fps", type=float, default=d.fps)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--source", default=d.source,
-                    choices=["synthetic", "camera", "camera-nv12"],
-                    help="camera-nv12: NV12 frames through the ring (needs --frame-height / "
-                         "--frame-width)")
+                    choices=["synthetic", "camera", "camera-nv12", "camera-jpeg"],
+                    help="camera-nv12: NV12 frames through the ring; camera-jpeg: Motion-JPEG "
+                         "files through the ring, decoded on the device (both need "
+                         "--frame-height / --frame-width)")
+    ap.add_argument("--jpeg-max-bytes", type=int, default=d.jpeg_max_bytes,
+                    help="camera-jpeg: bytes per compressed frame (0 = height x width / 2)")
     ap.add_argument("--no-native-loop", action="store_true")
     ap.add_argument("--steps-per-poll", type=int, default=d.steps_per_poll)
     ap.add_argument("--refine-s", type=float, default=d.refine_s,
@@ -227,7 +230,7 @@ def main(argv=None):
                        source=a.source, native_loop=not a.no_native_loop,
                        steps_per_poll=a.steps_per_poll, sync_every=a.sync_every,
                        refine_s=a.refine_s, frame_height=a.frame_height,
-                       frame_width=a.frame_width,
+                       frame_width=a.frame_width, jpeg_max_bytes=a.jpeg_max_bytes,
                        crops_per_image=a.crops_per_image, track=a.track,
                        track_iou=a.track_iou, track_max_age=a.track_max_age,
                        track_min_hits=a.track_min_hits,

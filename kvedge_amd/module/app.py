@@ -113,6 +113,47 @@ class _SimTempModel:
                 "timeCreated": now_iso()}
 
 
+def _jpeg_batch(batch: int, h: int, w: int, row_bytes: int, g) -> torch.Tensor:
+    """uint8 [batch, row_bytes]: baseline JPEG files (4:2:0, one restart interval per MCU row,
+    as camera firmware writes them) of blocky random pictures -- up to four distinct ones,
+    repeated over the batch rows.  Pillow encodes them when it is installed, else the
+    reference encoder; the quality steps down until a file fits its row."""
+    import numpy as np
+
+    from ..ops import reference as ref
+
+    pics = []
+    for _ in range(min(batch, 4)):
+        coarse = torch.randint(0, 256, (-(-h // 16), -(-w // 16), 3), dtype=torch.uint8,
+                               generator=g)
+        pics.append(coarse.repeat_interleave(16, 0).repeat_interleave(16, 1)[:h, :w]
+                    .contiguous().numpy())
+
+    def encode(pic, quality):
+        try:
+            from PIL import Image
+        except ImportError:
+            return ref.jpeg_encode(pic[None], "420", quality)[0]
+        import io
+
+        buf = io.BytesIO()
+        Image.fromarray(pic).save(buf, "JPEG", quality=quality, subsampling=2,
+                                  restart_marker_rows=1)
+        return buf.getvalue()
+
+    files = []
+    for pic in pics:
+        for quality in (75, 50, 25, 5):
+            f = encode(pic, quality)
+            if len(f) <= row_bytes:
+                break
+        else:
+            raise ValueError(f"a {h}x{w} frame does not fit jpeg_max_bytes = {row_bytes}")
+        files.append(f)
+    rows = ref.jpeg_rows([files[i % len(files)] for i in range(batch)], row_bytes)
+    return torch.from_numpy(np.ascontiguousarray(rows))
+
+
 class _CameraSource:
     """Host frame producer for source="camera" / "camera-nv12": cycles a few pre-rendered
     uint8 batches ([B, H, W, 3], or NV12 [B, H * 3 // 2, W])
@@ -121,14 +162,19 @@ class _CameraSource:
     thread; the hand-off path (pinned ring -> DMA in the native serve loop) is the
     production one."""
 
-    def __init__(self, ring, batch: int, hw, fps: float, seed: int, nv12: bool = False):
+    def __init__(self, ring, batch: int, hw, fps: float, seed: int, nv12: bool = False,
+                 jpeg_row_bytes: int = 0):
         import threading
 
         h, w = (hw, hw) if isinstance(hw, int) else hw  # square model size, or (height, width)
         g = torch.Generator().manual_seed(seed)
-        shape = (batch, h * 3 // 2, w) if nv12 else (batch, h, w, 3)
-        self.frames = [torch.randint(0, 256, shape, dtype=torch.uint8, generator=g)
-                       for _ in range(3)]
+        if jpeg_row_bytes:
+            # Motion-JPEG: the pre-rendered pictures are encoded once, one file per ring row
+            self.frames = [_jpeg_batch(batch, h, w, jpeg_row_bytes, g) for _ in range(3)]
+        else:
+            shape = (batch, h * 3 // 2, w) if nv12 else (batch, h, w, 3)
+            self.frames = [torch.randint(0, 256, shape, dtype=torch.uint8, generator=g)
+                           for _ in range(3)]
         self.ring, self.batch, self.fps = ring, batch, fps
         self.seq = 0
         self._stop = threading.Event()
@@ -205,6 +251,7 @@ class ModuleApp:
         self.views = None  # ops.CameraViews with `views` configured
         self.enhance = None  # ops.FrameEnhance with `enhance` on
         self.ring = None
+        self._decode_errors = 0
         self.camera: Optional[_CameraSource] = None
         self.sim: Optional[_SimTempModel] = None
         self.state = {"total_images": 0, "total_steps": 0, "restarts": 0, "rebuilds": 0,
@@ -515,7 +562,10 @@ class ModuleApp:
                                       streams=(edge_streams(cfg.batch)
                                                if dev.type == "cuda" and not cfg.gallery else 1),
                                       frame_hw=cfg.frame_hw(), frame_format=cfg.frame_format(),
-                                      views=self.views, enhance=self.enhance)
+                                      views=self.views, enhance=self.enhance,
+                                      frame_codec=cfg.frame_codec(),
+                                      jpeg_row_bytes=(cfg.jpeg_row_bytes()
+                                                      if cfg.frame_codec() == "jpeg" else None))
         self.engine.prepare(warmup=1, autotune=dev.type == "cuda",
                             tune_cache=self.tune_cache if dev.type == "cuda" else None,
                             refine_s=cfg.refine_s)
@@ -554,7 +604,9 @@ class ModuleApp:
             self.camera = _CameraSource(self.ring, cfg.batch,
                                         cfg.frame_hw() or cfg.resolved_image_size(), cfg.fps,
                                         cfg.seed + self.rank,
-                                        nv12=cfg.frame_format() == "nv12")
+                                        nv12=cfg.frame_format() == "nv12",
+                                        jpeg_row_bytes=(self.engine.jpeg.row_bytes
+                                                        if self.engine.jpeg is not None else 0))
 
     def _build_fleet(self, previous: Optional[ModuleConfig] = None) -> Optional[str]:
         """Build on every rank; if ANY rank failed (HBM exhausted, bad shape), every rank
@@ -641,6 +693,9 @@ class ModuleApp:
         self._win_imgs += self.cfg.batch * nsteps
         self.state["total_images"] += self.cfg.batch * nsteps
         self.state["total_steps"] += nsteps
+        if self.engine.decode_status is not None and nsteps > 0:
+            # Motion-JPEG: files of the last step the decoder refused or found damaged
+            self._decode_errors += int((self.engine.decode_status != 0).sum())
         if self.snapshots is not None and nsteps > 0 and self.engine.outputs is not None:
             # the pictures of the last step: lengths to the host, bytes only for what is sent
             totals = self.camera_totals.update() if self.camera_totals is not None else None
@@ -805,6 +860,8 @@ class ModuleApp:
                "source": self.cfg.source}
         if self.ring is not None:
             msg["frames_dropped"] = self.ring.dropped
+        if self.engine is not None and self.engine.decode_status is not None:
+            msg["decode_errors"] = self._decode_errors
         if self._gpu is not None and self.rank == 0:  # only rank 0 sends the message
             g = self._gpu.sample()
             if g:

@@ -13,7 +13,7 @@ from dataclasses import asdict, dataclass, fields, replace
 from typing import Any, Dict, Tuple
 
 MODELS = ("resnet50", "yolov8n", "detect-classify", "simulated-temperature")
-SOURCES = ("synthetic", "camera", "camera-nv12")
+SOURCES = ("synthetic", "camera", "camera-nv12", "camera-jpeg")
 DTYPES = ("bf16",)
 ZONE_ANCHORS = ("bottom", "centre")
 ENHANCE_MODES = ("on", "auto")  # `enhance` false is off
@@ -146,7 +146,14 @@ class ModuleConfig:
     # decoders deliver them (1.5 bytes per pixel through the ring and over PCIe instead of 3;
     # the colour conversion happens inside the on-device resample).  It needs frame_height /
     # frame_width (for model-size frames, set them to the model size)
+    # "camera-jpeg" = the cameras deliver Motion-JPEG: one baseline JPEG file per frame goes
+    # through the ring (about a tenth of the NV12 bytes) and is decoded on the device as the
+    # first op of the step (ops.jpeg_decode); everything after it sees RGB frames.  It needs
+    # frame_height / frame_width, the size every file must have
     source: str = "synthetic"
+    # source camera-jpeg: bytes reserved per compressed frame (a multiple of 16); 0 = frame
+    # height x width / 2 rounded up to 16.  A file that does not fit is dropped by the producer
+    jpeg_max_bytes: int = 0
     # native resolution of the incoming frames (e.g. 1080 x 1920); the engine resamples them
     # to the model size on the device (YOLO: letterbox, ResNet: resize + centre-crop) and
     # YOLO boxes are reported in frame pixels.  0 / 0 = frames arrive at model size
@@ -289,7 +296,8 @@ class ModuleConfig:
 
     # keys that force an engine rebuild when they change
     REBUILD = ("model", "batch", "dtype", "seed", "image_size", "conf", "iou", "max_det",
-               "use_graph", "source", "frame_height", "frame_width", "crops_per_image",
+               "use_graph", "source", "jpeg_max_bytes", "frame_height", "frame_width",
+               "crops_per_image",
                "track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks",
                "lines", "zones", "zone_anchor", "watch", "watch_cell", "watch_row_step",
                "watch_bg_shift", "watch_regions", "watch_region_max",
@@ -339,6 +347,12 @@ class ModuleConfig:
                                  "frames at model size, set them to the model size)")
             if self.frame_height % 2:
                 raise ValueError("source camera-nv12 needs an even frame_height")
+        if self.source == "camera-jpeg" and not self.frame_height:
+            raise ValueError("source camera-jpeg needs frame_height and frame_width: the size "
+                             "of the frames in the files")
+        if self.jpeg_max_bytes and (self.jpeg_max_bytes % 16 or
+                                    not 1024 <= self.jpeg_max_bytes <= 1 << 28):
+            raise ValueError("jpeg_max_bytes must be 0 or a multiple of 16 in 1024..2^28")
         if not 1 <= self.crops_per_image <= 16:
             raise ValueError("crops_per_image must be 1..16")
         if self.model == "detect-classify":  # cross-key limits bind the cascade only
@@ -598,11 +612,21 @@ class ModuleConfig:
 
     def is_camera(self) -> bool:
         """A host producer feeds the ring (any frame format)."""
-        return self.source in ("camera", "camera-nv12")
+        return self.source in ("camera", "camera-nv12", "camera-jpeg")
 
     def frame_format(self) -> str:
         """Format of the incoming frames (InferenceEngine frame_format)."""
         return "nv12" if self.source == "camera-nv12" else "rgb"
+
+    def frame_codec(self) -> str:
+        """How the frames are compressed on their way in (InferenceEngine frame_codec)."""
+        return "jpeg" if self.source == "camera-jpeg" else "raw"
+
+    def jpeg_row_bytes(self) -> int:
+        """Bytes per compressed frame of source camera-jpeg."""
+        from ..ops import jpeg_row_bytes
+
+        return self.jpeg_max_bytes or jpeg_row_bytes(self.frame_hw())
 
     TRACK_KEYS = ("track", "track_iou", "track_max_age", "track_min_hits", "track_max_tracks")
     ZONE_KEYS = ("lines", "zones", "zone_anchor")
@@ -674,6 +698,9 @@ class ModuleConfig:
                 d.pop(k)
         else:
             d["lines"], d["zones"] = list(d["lines"]), list(d["zones"])
+        # jpeg_max_bytes belongs to source camera-jpeg
+        if self.source != "camera-jpeg":
+            d.pop("jpeg_max_bytes")
         # and the views
         if self.views:
             d["views"] = list(d["views"])

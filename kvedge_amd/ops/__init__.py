@@ -2560,6 +2560,104 @@ def jpeg_encode(images: torch.Tensor, enc: JpegEncoder, out: Optional[torch.Tens
 
 
 # ---------------------------------------------------------------------------
+# MJPEG camera sources: baseline JPEG files decoded on the device
+# ---------------------------------------------------------------------------
+JPEG_DECODE_ERRORS = _ref.JPEG_DECODE_ERRORS
+JPEG_DECODE_TABLE_BYTES = 6256  # sizeof(JdTables), csrc/kernels/jpeg_decode_core.h
+JPEG_DECODE_LANES = (16, 32, 64)
+
+
+def jpeg_row_bytes(hw) -> int:
+    """Default size of a compressed-frame row: H * W // 2 rounded up to 16 (a third of the
+    NV12 frame; camera JPEGs are near a tenth of it)."""
+    return max(16, -(-(int(hw[0]) * int(hw[1]) // 2) // 16) * 16)
+
+
+class JpegDecoder:
+    """Everything :func:`jpeg_decode` needs outside the caller's tensors, for ``streams``
+    files of ``hw`` = (H, W) pixels in rows of ``row_bytes`` bytes (a multiple of 16), all in
+    device memory: ``tables`` uint8 [streams, 6256] (per file: scan geometry, error bits, its
+    quantisation and Huffman tables), ``mpos`` int32 [streams, ceil(H / 8) * ceil(W / 8)]
+    (offsets of the restart markers; the worst case is 4:4:4 with one MCU per interval),
+    ``planes`` uint8 [streams, 3, H16, W16] (the Y / Cb / Cr samples before upsampling, H16 /
+    W16 = H / W rounded up to 16) and ``status`` int32 [streams].  The op allocates nothing.
+    ``lanes``: restart intervals per wavefront of the decode launch (16, 32 or 64); fewer
+    lanes give more wavefronts when streams x intervals is small."""
+
+    def __init__(self, streams: int, hw, row_bytes: Optional[int] = None, device="cpu",
+                 lanes: int = 16):
+        h, w = int(hw[0]), int(hw[1])
+        if not (1 <= h <= JPEG_MAX_EXTENT and 1 <= w <= JPEG_MAX_EXTENT):
+            raise ValueError(f"JPEG image size {h}x{w} outside 1..{JPEG_MAX_EXTENT}")
+        if isinstance(streams, bool) or not 1 <= int(streams) <= 65535:
+            raise ValueError(f"streams must be in 1..65535, got {streams!r}")
+        row_bytes = jpeg_row_bytes((h, w)) if row_bytes is None else int(row_bytes)
+        if row_bytes < 16 or row_bytes % 16 or row_bytes > 0x7ffffff0:
+            raise ValueError(f"row_bytes must be a multiple of 16 in 16..2^31-16, got {row_bytes}")
+        if lanes not in JPEG_DECODE_LANES:
+            raise ValueError(f"lanes must be one of {JPEG_DECODE_LANES}, got {lanes!r}")
+        self.streams, self.hw, self.row_bytes, self.lanes = int(streams), (h, w), row_bytes, lanes
+        dev = torch.device(device)
+        self.status = torch.zeros(self.streams, dtype=torch.int32, device=dev)
+        if dev.type == "cuda":
+            h16, w16 = -(-h // 16) * 16, -(-w // 16) * 16
+            self.tables = torch.zeros(self.streams, JPEG_DECODE_TABLE_BYTES, dtype=torch.uint8,
+                                      device=dev)
+            self.mpos = torch.zeros(self.streams, -(-h // 8) * -(-w // 8), dtype=torch.int32,
+                                    device=dev)
+            self.planes = torch.zeros(self.streams, 3, h16, w16, dtype=torch.uint8, device=dev)
+        else:
+            self.tables = self.mpos = self.planes = None  # the reference needs none
+
+    @property
+    def device(self) -> torch.device:
+        return self.status.device
+
+
+def jpeg_decode(files: torch.Tensor, dec: JpegDecoder, out: Optional[torch.Tensor] = None,
+                slot0: int = 0):
+    """Baseline JPEG ``files`` uint8 [N, dec.row_bytes] (one file per row from SOI, bytes after
+    EOI ignored) -> ``(rgb, status)``: ``rgb`` uint8 [N, H, W, 3] is ``out`` or new, ``status``
+    int32 [N] is rows ``slot0 .. slot0 + N`` of ``dec.status``: 0, or minus the sum of the
+    JPEG_DECODE_ERRORS bits.  A header error (unsupported form, wrong size, missing table,
+    truncated header) zero-fills the image; an entropy error zeroes the rest of its restart
+    interval.  What is accepted and every rule is written out at ops.reference.jpeg_decode; GPU
+    and CPU agree byte for byte, status and malformed files included.  Three launches on the
+    current stream (csrc/kernels/jpeg_decode.hip), no allocation when ``out`` is given, no host
+    synchronisation, capturable.  File n works in row ``slot0 + n`` of the decoder's scratch."""
+    if not isinstance(dec, JpegDecoder):
+        raise TypeError(f"dec must be an ops.JpegDecoder, got {type(dec).__name__}")
+    if (files.dtype != torch.uint8 or files.dim() != 2 or files.shape[1] != dec.row_bytes
+            or not files.is_contiguous()):
+        raise ValueError(f"files are contiguous uint8 [N, {dec.row_bytes}], got {files.dtype} "
+                         f"{tuple(files.shape)}")
+    n, slot0 = int(files.shape[0]), int(slot0)
+    if slot0 < 0 or slot0 + n > dec.streams:
+        raise ValueError(f"files [{slot0}, {slot0 + n}) outside the {dec.streams} the decoder "
+                         f"was made for")
+    if files.device != dec.device:
+        raise ValueError(f"files on {files.device}, decoder on {dec.device}")
+    if files.data_ptr() % 16:
+        raise ValueError("files must be 16-byte aligned")
+    h, w = dec.hw
+    if out is None:
+        out = empty(n, h, w, 3, dtype=torch.uint8, device=files.device)
+    if (out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous()
+            or out.device != files.device):
+        raise ValueError(f"out must be contiguous uint8 [{n}, {h}, {w}, 3] on {files.device}")
+    rows = slice(slot0, slot0 + n)
+    status = dec.status[rows]
+    if files.is_cuda:
+        _native().jpeg_decode(files, dec.tables[rows], dec.mpos[rows], dec.planes[rows], out,
+                              status, dec.lanes)
+    else:
+        rgb, st = _ref.jpeg_decode(files, dec.hw)
+        out.copy_(torch.from_numpy(rgb))
+        status.copy_(torch.from_numpy(st))
+    return out, status
+
+
+# ---------------------------------------------------------------------------
 # snapshot annotation: boxes, labels and a privacy mosaic drawn into the thumbnails
 # ---------------------------------------------------------------------------
 ANNOTATE_TABLE_STRIDE = _ref.ANN_TABLE_STRIDE

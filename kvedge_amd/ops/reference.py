@@ -1061,6 +1061,368 @@ def jpeg_encode(images, subsampling: str = "420", quality: int = 75, stats: bool
 
 
 # ---------------------------------------------------------------------------
+# baseline JPEG decoder (csrc/kernels/jpeg_decode.hip, jpeg_decode_core.h): MJPEG camera frames
+# ---------------------------------------------------------------------------
+# status = -(sum of the bits below).  The first six are header errors: the image is zero-filled.
+JPEG_DECODE_ERRORS = {"marker": 1, "truncated": 2, "unsupported": 4, "size": 8, "missing": 16,
+                      "huffman_table": 32, "entropy": 64, "intervals": 128, "no_eoi": 256}
+JPEG_DECODE_HEADER_ERRORS = 63
+JPEG_DECODE_MAX_SEGMENTS = 256
+
+
+def jpeg_rows(files, row_bytes: int) -> np.ndarray:
+    """uint8 [N, row_bytes]: one file per row from byte 0, zero padded."""
+    out = np.zeros((len(files), int(row_bytes)), np.uint8)
+    for i, f in enumerate(files):
+        if len(f) > row_bytes:
+            raise ValueError(f"file {i} has {len(f)} bytes, a row holds {row_bytes}")
+        out[i, :len(f)] = np.frombuffer(bytes(f), np.uint8)
+    return out
+
+
+def _jd_build_huff(bits, vals):
+    """(look, maxcode, valoff, val) of one DHT table or None when it is no prefix code: look
+    [512] = symbol | length << 8 for every 9-bit prefix of a code of <= 9 bits (0: longer),
+    maxcode[l] the largest code of length l or -1, valoff[l] = first symbol index - first code."""
+    look, maxcode, valoff = [0] * 512, [-1] * 17, [0] * 17
+    val = list(vals) + [0] * (256 - len(vals))
+    code = k = 0
+    for ln in range(1, 17):
+        n = bits[ln - 1]
+        if code + n > (1 << ln):
+            return None
+        valoff[ln] = k - code
+        maxcode[ln] = code + n - 1 if n else -1
+        if ln <= 9:
+            rep = 1 << (9 - ln)
+            for c in range(n):
+                look[(code + c) * rep:(code + c + 1) * rep] = [vals[k + c] | (ln << 8)] * rep
+        k += n
+        code = (code + n) << 1
+    return look, maxcode, valoff, val
+
+
+def jpeg_parse_header(p: bytes, hw):
+    """Walk SOI .. SOS of one row.  Returns (error bit or 0, info): info has the quantisation
+    tables ``q`` {id: [64] natural order}, the Huffman tables ``h`` {class * 2 + id: ...}, the
+    luma sampling ``hs`` / ``vs``, the per-component table ids ``tq`` / ``td`` / ``ta``, the
+    restart interval ``ri`` (0: none), the MCU grid ``mw`` / ``mh``, the offset ``e0`` of the
+    first entropy byte and the number of restart intervals ``expected``.  The rules, in order,
+    are those of jd_parse_header (csrc/kernels/jpeg_decode_core.h)."""
+    E = JPEG_DECODE_ERRORS
+    n, (H, W) = len(p), hw
+    info = dict(q={}, h={}, hs=1, vs=1, tq=[0] * 3, td=[0] * 3, ta=[0] * 3, ri=0)
+    if n < 4 or p[0] != 0xff or p[1] != 0xd8:
+        return E["marker"], info
+    pos, sof, cid = 2, False, [0] * 3
+    be16 = lambda o: (p[o] << 8) | p[o + 1]  # noqa: E731
+    for _ in range(JPEG_DECODE_MAX_SEGMENTS):
+        if pos + 4 > n:
+            return E["truncated"], info
+        if p[pos] != 0xff:
+            return E["marker"], info
+        m = p[pos + 1]
+        if m in (0, 1, 0xff) or 0xd0 <= m <= 0xd9:
+            return E["marker"], info
+        ln = be16(pos + 2)
+        if ln < 2 or pos + 2 + ln > n:
+            return E["truncated"], info
+        s, sl = pos + 4, ln - 2
+        if m == 0xdb:
+            q = 0
+            for _it in range(4):
+                if q >= sl:
+                    break
+                pq = p[s + q]
+                if pq >> 4 or (pq & 15) > 3:
+                    return E["unsupported"], info
+                if q + 65 > sl:
+                    return E["truncated"], info
+                tab = [0] * 64
+                for i in range(64):
+                    tab[JPEG_ZIGZAG[i]] = p[s + q + 1 + i]
+                info["q"][pq & 3] = tab
+                q += 65
+            if q != sl:
+                return E["marker"], info
+        elif m == 0xc4:
+            q = 0
+            for _it in range(4):
+                if q >= sl:
+                    break
+                if q + 17 > sl:
+                    return E["truncated"], info
+                tc, th = p[s + q] >> 4, p[s + q] & 15
+                if tc > 1 or th > 1:
+                    return E["unsupported"], info
+                bits = list(p[s + q + 1:s + q + 17])
+                total = sum(bits)
+                if total > 256:
+                    return E["huffman_table"], info
+                if q + 17 + total > sl:
+                    return E["truncated"], info
+                tab = _jd_build_huff(bits, list(p[s + q + 17:s + q + 17 + total]))
+                if tab is None:
+                    return E["huffman_table"], info
+                info["h"][tc * 2 + th] = tab
+                q += 17 + total
+            if q != sl:
+                return E["marker"], info
+        elif m == 0xc0:
+            if sof:
+                return E["marker"], info
+            if sl < 6:
+                return E["truncated"], info
+            if p[s] != 8 or p[s + 5] != 3:
+                return E["unsupported"], info
+            if sl != 15:
+                return E["marker"], info
+            if be16(s + 1) != H or be16(s + 3) != W:
+                return E["size"], info
+            for c in range(3):
+                cid[c], hv, info["tq"][c] = p[s + 6 + 3 * c], p[s + 7 + 3 * c], p[s + 8 + 3 * c]
+                if info["tq"][c] > 3:
+                    return E["unsupported"], info
+                if hv not in ((0x11, 0x21, 0x22) if c == 0 else (0x11,)):
+                    return E["unsupported"], info
+                if c == 0:
+                    info["hs"], info["vs"] = hv >> 4, hv & 15
+            sof = True
+        elif 0xc1 <= m <= 0xcf:
+            return E["unsupported"], info
+        elif m == 0xdd:
+            if sl != 2:
+                return E["marker"], info
+            info["ri"] = be16(s)
+        elif m == 0xda:
+            if not sof:
+                return E["missing"], info
+            if sl != 10 or p[s] != 3:
+                return E["unsupported"], info
+            for c in range(3):
+                if p[s + 1 + 2 * c] != cid[c]:
+                    return E["unsupported"], info
+                info["td"][c], info["ta"][c] = p[s + 2 + 2 * c] >> 4, p[s + 2 + 2 * c] & 15
+                if info["td"][c] > 1 or info["ta"][c] > 1:
+                    return E["unsupported"], info
+            if p[s + 7] != 0 or p[s + 8] != 63 or p[s + 9] != 0:
+                return E["unsupported"], info
+            for c in range(3):
+                if (info["tq"][c] not in info["q"] or info["td"][c] not in info["h"]
+                        or 2 + info["ta"][c] not in info["h"]):
+                    return E["missing"], info
+            info["e0"] = pos + 2 + ln
+            info["mw"] = -(-W // (8 * info["hs"]))
+            info["mh"] = -(-H // (8 * info["vs"]))
+            mcus = info["mw"] * info["mh"]
+            info["expected"] = -(-mcus // info["ri"]) if info["ri"] else 1
+            return 0, info
+        elif not (0xe0 <= m <= 0xef or m == 0xfe):
+            return E["unsupported"], info
+        pos += 2 + ln
+    return E["unsupported"], info
+
+
+class _JdBits:
+    """MSB-first reader of one restart interval: FF 00 reads as FF, past the end reads 0."""
+
+    def __init__(self, data: bytes):
+        self.d = data.replace(b"\xff\x00", b"\xff")
+        self.total = 8 * len(self.d)
+        self.c = 0
+
+    def peek(self, n):  # n <= 16
+        i = self.c >> 3
+        w = int.from_bytes(self.d[i:i + 4].ljust(4, b"\0"), "big")
+        return (w >> (32 - (self.c & 7) - n)) & ((1 << n) - 1)
+
+    def symbol(self, tab):
+        look, maxcode, valoff, val = tab
+        e = look[self.peek(9)]
+        if e:
+            self.c += e >> 8
+            return e & 255
+        for ln in range(10, 17):
+            code = self.peek(ln)
+            if code <= maxcode[ln]:
+                self.c += ln
+                return val[(code + valoff[ln]) & 255]
+        return -1
+
+    def extend(self, s):  # 1 <= s <= 15
+        v = self.peek(s)
+        self.c += s
+        return v - (1 << s) + 1 if v < (1 << (s - 1)) else v
+
+
+def _jd_block(rd, dc, ac, pred):
+    """One block: ([64] natural-order coefficients, new predictor) or None on an invalid code,
+    a DC category above 15, a coefficient index past 63 or an interval that ran out of bits."""
+    s = rd.symbol(dc)
+    if s < 0 or s > 15:
+        return None
+    if s:
+        pred += rd.extend(s)
+    out = [0] * 64
+    out[0] = ((pred + 32768) & 0xffff) - 32768
+    k = 1
+    for _ in range(63):
+        if k >= 64:
+            break
+        sym = rd.symbol(ac)
+        if sym < 0:
+            return None
+        run, s = sym >> 4, sym & 15
+        if s == 0:
+            if run != 15:
+                break
+            k += 16
+            continue
+        k += run
+        if k > 63:
+            return None
+        out[JPEG_ZIGZAG[k]] = rd.extend(s)
+        k += 1
+    return None if rd.c > rd.total else (out, pred)
+
+
+def _jd_idct_pass(d, shift):
+    """libjpeg's slow integer IDCT (jidctint.c), one 8-point pass along the last axis of an
+    int32 array; the arithmetic wraps modulo 2^32 as the kernels' does."""
+    d0, d1, d2, d3, d4, d5, d6, d7 = (d[..., i] for i in range(8))
+    z1 = (d2 + d6) * 4433
+    t2, t3 = z1 - d6 * 15137, z1 + d2 * 6270
+    t0, t1 = (d0 + d4) << 13, (d0 - d4) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = d7, d5, d3, d1
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2 = z1 * -7373, z2 * -20995
+    z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    r = np.int32(1 << (shift - 1))
+    o = [t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3]
+    return np.stack([(v + r) >> shift for v in o], axis=-1)
+
+
+def _jd_samples(coef, q):
+    """int32 [..., 64] natural-order coefficients x [64] quantisers -> uint8 [..., 8, 8]."""
+    with np.errstate(over="ignore"):
+        c = (coef.astype(np.int32) * np.asarray(q, np.int32)).reshape(coef.shape[:-1] + (8, 8))
+        ws = _jd_idct_pass(c.swapaxes(-1, -2), 11).swapaxes(-1, -2)   # columns
+        px = _jd_idct_pass(ws, 18) & 1023                                # rows
+    # libjpeg's range_limit table behind its 10-bit mask, the +128 level shift in it
+    return np.where(px < 128, px + 128, np.where(px < 512, 255, np.where(px < 896, 0, px - 896))
+                    ).astype(np.uint8)
+
+
+def _jd_upsample(c, hs, vs, H, W):
+    """libjpeg's "fancy" triangle upsampling of a chroma plane whose real samples are
+    ceil(H / vs) x ceil(W / hs); edges replicate (indices clamp)."""
+    ch, cw = -(-H // vs), -(-W // hs)
+    c = c[:ch, :cw].astype(np.int32)
+    if hs == 1:
+        return c
+    x, y = np.arange(W), np.arange(H)
+    i = x >> 1
+    j = np.clip(np.where(x & 1, i + 1, i - 1), 0, cw - 1)
+    if vs == 1:
+        return (3 * c[:, i] + c[:, j] + np.where(x & 1, 2, 1)) >> 2
+    rn = y >> 1
+    rf = np.clip(np.where(y & 1, rn + 1, rn - 1), 0, ch - 1)
+    a = 3 * c[rn] + c[rf]
+    return (3 * a[:, i] + a[:, j] + np.where(x & 1, 7, 8)) >> 4
+
+
+def jpeg_decode_one(p: bytes, hw):
+    """(uint8 [H, W, 3] RGB, status) of one row ``p`` holding a file from SOI."""
+    E = JPEG_DECODE_ERRORS
+    H, W = int(hw[0]), int(hw[1])
+    n = len(p)
+    err, I = jpeg_parse_header(p, (H, W))
+    if err:
+        return np.zeros((H, W, 3), np.uint8), -err
+    # restart and EOI markers in file order, up to the first EOI
+    mpos, eoi, i = [], False, p.find(b"\xff", I["e0"])
+    while 0 <= i < n - 1:
+        if 0xd0 <= p[i + 1] <= 0xd7:
+            mpos.append(i)
+        elif p[i + 1] == 0xd9:
+            mpos.append(i)
+            eoi = True
+            break
+        i = p.find(b"\xff", i + 1)
+    nmark = len(mpos)
+    present = nmark if eoi else nmark + 1
+    err = (0 if eoi else E["no_eoi"]) | (E["intervals"] if present != I["expected"] else 0)
+    hs, vs, mw, mh, ri = I["hs"], I["vs"], I["mw"], I["mh"], I["ri"]
+    ny = hs * vs
+    bpm, mcus = ny + 2, mw * mh
+    comp = [0] * ny + [1, 2]
+    coef = np.zeros((mcus, bpm, 64), np.int32)
+    per = ri if ri else mcus
+    for k in range(min(present, I["expected"])):
+        start = I["e0"] if k == 0 else min(mpos[k - 1] + 2, n)
+        stop = max(mpos[k] if k < nmark else n, start)
+        rd = _JdBits(p[start:stop])
+        pred = [0, 0, 0]
+        failed = False
+        for m in range(k * per, min((k + 1) * per, mcus)):
+            for b in range(bpm):
+                c = comp[b]
+                got = _jd_block(rd, I["h"][I["td"][c]], I["h"][2 + I["ta"][c]], pred[c])
+                if got is None:  # this block and the rest of the interval stay zero
+                    failed = True
+                    err |= E["entropy"]
+                    break
+                coef[m, b], pred[c] = got
+            if failed:
+                break
+    px = np.stack([_jd_samples(coef[:, b], I["q"][I["tq"][comp[b]]]) for b in range(bpm)], 1)
+    px = px.reshape(mh, mw, bpm, 8, 8)
+    yp = px[:, :, :ny].reshape(mh, mw, vs, hs, 8, 8).transpose(0, 2, 4, 1, 3, 5)
+    yp = yp.reshape(mh * vs * 8, mw * hs * 8)[:H, :W].astype(np.int32)
+    cb, cr = (_jd_upsample(px[:, :, ny + c].transpose(0, 2, 1, 3).reshape(mh * 8, mw * 8),
+                           hs, vs, H, W) - 128 for c in range(2))
+    # libjpeg's 16-bit fixed-point JFIF YCbCr -> RGB (jdcolor.c)
+    r = yp + ((91881 * cr + 32768) >> 16)
+    g = yp + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = yp + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8), -err
+
+
+def jpeg_decode(files, hw):
+    """Baseline JPEG files -> (uint8 [N, H, W, 3] RGB, int32 [N] status): THE definition the
+    HIP kernels (csrc/kernels/jpeg_decode.hip) equal byte for byte, malformed files included.
+    ``files`` uint8 [N, row_bytes]: one file per row from SOI (see :func:`jpeg_rows`); bytes
+    after EOI are ignored.
+
+    Accepted: baseline sequential (SOF0), 8 bit, three components with 4:4:4, 4:2:2 (2x1) or
+    4:2:0 sampling, one interleaved scan, 8-bit quantisation tables and up to 2 DC + 2 AC Huffman
+    tables from the file's own DQT / DHT segments, any DRI or none, APPn / COM skipped, frame
+    size equal to ``hw``.  Anything else is a header error: status = -bit
+    (JPEG_DECODE_ERRORS) and a zero image.  After a good header: the entropy bytes are cut at
+    FF D0..D7 and at the first FF D9 into restart intervals (``no_eoi`` when the row holds no
+    EOI: the last interval then runs to the end of the row; ``intervals`` when their number is
+    not the expected one; intervals past the expected number are ignored, missing ones decode as
+    all-zero coefficients).  Each interval starts with DC predictors 0; an invalid Huffman code,
+    a DC category above 15, a coefficient index past 63 or reading past the interval's last bit
+    sets ``entropy`` and leaves that block and the rest of the interval all zero.  Then, as
+    libjpeg does: dequantise, the slow integer IDCT (13-bit constants, 2 pass-1 bits, columns
+    first), +128 and the masked range limit, "fancy" triangle chroma upsampling with
+    replicated edges, 16-bit fixed-point JFIF YCbCr -> RGB."""
+    arr = files.numpy() if isinstance(files, torch.Tensor) else np.asarray(files)
+    if arr.dtype != np.uint8 or arr.ndim != 2:
+        raise ValueError(f"files are uint8 [N, row_bytes], got {arr.dtype} {arr.shape}")
+    out = np.zeros((arr.shape[0], int(hw[0]), int(hw[1]), 3), np.uint8)
+    status = np.zeros(arr.shape[0], np.int32)
+    for i, row in enumerate(arr):
+        out[i], status[i] = jpeg_decode_one(row.tobytes(), hw)
+    return out, status
+
+
+# ---------------------------------------------------------------------------
 # snapshot annotation: boxes, labels and privacy mosaic drawn into the thumbnails
 # ---------------------------------------------------------------------------
 # style table, int32 per camera (the layout csrc/kernels/annotate.hip reads)
