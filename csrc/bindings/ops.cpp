@@ -1171,8 +1171,10 @@ void jpeg_encode(const at::Tensor& images, const at::Tensor& qtab, const at::Ten
 // file per row; tables / mpos / planes are the workspaces of an ops.JpegDecoder made for
 // (H, W) and row_bytes; out uint8 [N,H,W,3], status int32 [N].  Everything is validated before
 // the first launch.
-void jpeg_decode(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
-                 at::Tensor& planes, at::Tensor& out, at::Tensor& status, int64_t lanes) {
+static void jpeg_decode_any(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
+                            at::Tensor& planes, at::Tensor& out, at::Tensor& status,
+                            at::Tensor* split, at::Tensor* done, at::Tensor* paths,
+                            int64_t lanes, int64_t mode, int64_t launches) {
   check_dev(files, "files");
   check_dev(tables, "tables");
   check_dev(mpos, "mpos");
@@ -1207,12 +1209,49 @@ void jpeg_decode(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
        std::initializer_list<const at::Tensor*>{&tables, &mpos, &planes, &out, &status})
     TORCH_CHECK(t->device() == files.device(), "kvedge: jpeg_decode operands on different devices");
   const c10::DeviceGuard g(files.device());
-  const int rc = kv_jpeg_decode(files.data_ptr<uint8_t>(), tables.data_ptr<uint8_t>(),
-                                mpos.data_ptr<int>(), planes.data_ptr<uint8_t>(),
-                                out.data_ptr<uint8_t>(), status.data_ptr<int>(), (int)N,
-                                (long long)files.size(1), (int)H, (int)W, (int)lanes,
-                                cur_stream(files));
+  int rc;
+  if (!split) {
+    rc = kv_jpeg_decode(files.data_ptr<uint8_t>(), tables.data_ptr<uint8_t>(),
+                        mpos.data_ptr<int>(), planes.data_ptr<uint8_t>(),
+                        out.data_ptr<uint8_t>(), status.data_ptr<int>(), (int)N,
+                        (long long)files.size(1), (int)H, (int)W, (int)lanes, cur_stream(files));
+  } else {
+    TORCH_CHECK(mode >= 0 && mode <= 2 && launches >= 1 && launches <= 7,
+                "kvedge: jpeg_decode_split mode 0/1/2, launches 1..7");
+    const int64_t ints = kv_jpeg_decode_split_ints(files.size(1));
+    const int64_t want[3] = {N * ints, N * max_int, N * 2};
+    const at::Tensor* ws[3] = {split, done, paths};
+    for (int i = 0; i < 3; ++i) {
+      check_dev(*ws[i], "split scratch");
+      TORCH_CHECK(ws[i]->scalar_type() == at::kInt && ws[i]->is_contiguous() &&
+                      ws[i]->numel() >= want[i] && ws[i]->device() == files.device(),
+                  "kvedge: jpeg_decode_split split int32 [N,", ints, "], done int32 [N,", max_int,
+                  "], paths int32 [N,2] on the files' device");
+    }
+    rc = kv_jpeg_decode_split(files.data_ptr<uint8_t>(), tables.data_ptr<uint8_t>(),
+                              mpos.data_ptr<int>(), planes.data_ptr<uint8_t>(),
+                              out.data_ptr<uint8_t>(), status.data_ptr<int>(),
+                              split->data_ptr<int>(), done->data_ptr<int>(),
+                              paths->data_ptr<int>(), (int)N, (long long)files.size(1), (int)H,
+                              (int)W, (int)lanes, (int)mode, (int)launches,
+                              cur_stream(files));
+  }
   TORCH_CHECK(rc == 0, "kvedge: jpeg_decode failed rc=", rc);
+}
+// int32 per file of an ops.JpegDecoder's split scratch
+int64_t jpeg_decode_split_ints(int64_t row_bytes) { return kv_jpeg_decode_split_ints(row_bytes); }
+void jpeg_decode(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
+                 at::Tensor& planes, at::Tensor& out, at::Tensor& status, int64_t lanes) {
+  jpeg_decode_any(files, tables, mpos, planes, out, status, nullptr, nullptr, nullptr, lanes, 0, 7);
+}
+// The same with the split launches for long restart intervals (mode 1: longer than sixteen
+// subsequences, 2: longer than one); split / done / paths are the decoder's extra scratch.
+void jpeg_decode_split(const at::Tensor& files, at::Tensor& tables, at::Tensor& mpos,
+                       at::Tensor& planes, at::Tensor& out, at::Tensor& status, at::Tensor& split,
+                       at::Tensor& done, at::Tensor& paths, int64_t lanes, int64_t mode,
+                       int64_t launches) {
+  jpeg_decode_any(files, tables, mpos, planes, out, status, &split, &done, &paths, lanes, mode,
+                  launches);
 }
 
 // K22: snapshot annotation (csrc/kernels/annotate.hip).  images uint8 [N,H,W,3], drawn in
@@ -1545,6 +1584,10 @@ TORCH_LIBRARY(kvedge, m) {
         "-> ()");
   m.def("jpeg_decode(Tensor files, Tensor(a!) tables, Tensor(b!) mpos, Tensor(c!) planes, "
         "Tensor(d!) out, Tensor(e!) status, int lanes) -> ()");
+  m.def("jpeg_decode_split(Tensor files, Tensor(a!) tables, Tensor(b!) mpos, Tensor(c!) planes, "
+        "Tensor(d!) out, Tensor(e!) status, Tensor(f!) split, Tensor(g!) done, Tensor(h!) paths, "
+        "int lanes, int mode, int launches) -> ()");
+  m.def("jpeg_decode_split_ints(int row_bytes) -> int", jpeg_decode_split_ints);
   m.def("annotate(Tensor(a!) images, Tensor table, Tensor font, Tensor? det, Tensor? count, "
         "Tensor? track_id, int Hs, int Ws, int slot0) -> ()");
   m.def("motion_blobs(Tensor mask, Tensor params, Tensor ignore, Tensor(a!) det, Tensor(b!) count, "
@@ -1606,6 +1649,7 @@ TORCH_LIBRARY_IMPL(kvedge, CUDA, m) {
   m.impl("frame_enhance", frame_enhance);
   m.impl("jpeg_encode", jpeg_encode);
   m.impl("jpeg_decode", jpeg_decode);
+  m.impl("jpeg_decode_split", jpeg_decode_split);
   m.impl("annotate", annotate);
   m.impl("motion_blobs", motion_blobs);
   m.impl("embed_quantize", embed_quantize);

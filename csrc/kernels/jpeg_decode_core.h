@@ -290,6 +290,21 @@ JD_HD int jd_decode_block(JdReader& r, const JdHuff& dc, const JdHuff& ac, int& 
   return r.overrun() ? 1 : 0;
 }
 
+// Bounds of restart interval k in the n-byte row: mp holds the marker offsets the scan found
+// (read back from scratch, so clamped to the row), max_int entries at most.
+JD_HD void jd_interval(const JdInfo& I, const int* mp, int k, int n, int max_int, int& start,
+                       int& stop) {
+  const int cap = I.expected < max_int ? I.expected : max_int;
+  const int a = k == 0 ? I.e0 : mp[k - 1 < cap - 1 ? k - 1 : cap - 1] + 2;
+  start = a < 0 ? 0 : a > n ? n : a;
+  stop = n;
+  if (k < I.nmark) {
+    const int b = mp[k < cap - 1 ? k : cap - 1];
+    stop = b < 0 ? 0 : b > n ? n : b;
+  }
+  if (stop < start) stop = start;
+}
+
 // libjpeg's slow integer IDCT (jidctint.c): 13-bit constants, one 8-point pass.  Arithmetic
 // wraps modulo 2^32 (as int32 arrays do in the reference), shifts are arithmetic.
 JD_HD uint32_t jd_sra(uint32_t x, int n) { return (uint32_t)((int32_t)x >> n); }
@@ -376,6 +391,206 @@ JD_HD void jd_rgb(int y, int cb, int cr, int& r, int& g, int& b) {
   r = jd_clampi(y + ((91881 * cr + 32768) >> 16), 0, 255);
   g = jd_clampi(y + ((-22554 * cb - 46802 * cr + 32768) >> 16), 0, 255);
   b = jd_clampi(y + ((116130 * cb + 32768) >> 16), 0, 255);
+}
+
+// ---------------------------------------------------------------------------------------------
+// A long restart interval decoded by many lanes.  The interval is cut at the row's multiples of
+// kJdSplitBytes into subsequences, one lane each.  Huffman streams self-synchronise, so a lane
+// that starts cold at its first bit soon walks the serial decoder's symbols; the lanes then
+// exchange end states until lane i starts exactly where lane i - 1 stopped, which makes their
+// concatenation the serial decode.  These are the per-lane steps; who runs which lane when is
+// the caller's business (the kernels in jpeg_decode.hip, the host self-test lane by lane).
+//
+// A decoder state sits at a symbol boundary: the row byte and bit of the next symbol, the block
+// of the MCU it belongs to and the zigzag index it continues at (0: the next symbol is a DC
+// code).  A symbol is a Huffman code with its extra bits.  The byte of a state is never the 00
+// of an FF 00 pair, so equal positions have equal states.
+// S, a multiple of the row's 16-byte words.  64 rather than the first guess of 128: the longest
+// block a baseline encoder writes for 8-bit noise is near 117 bytes, and at 64 such blocks
+// cover whole subsequences, so lanes that start and end inside one block occur in ordinary
+// files (and in the tests) rather than never.
+constexpr int kJdSplitBytes = 64;
+// "auto" splits intervals longer than this: where the probe's sweep of the interval length has
+// the split path level with the one-lane walk (b64 1080p 4:2:0 q75: 40 MCUs, about 1000 bytes)
+constexpr int kJdAutoSplitBytes = 16 * kJdSplitBytes;
+constexpr int kJdSplitSymbols = 8 * kJdSplitBytes;    // a symbol has at least one bit
+constexpr int kJdSplitBlocks = 4 * kJdSplitBytes + 1;  // a block has at least two
+constexpr int jd_lanes_per_row(long long row_bytes) {  // every interval longer than S fits
+  return (int)(3 * (row_bytes / kJdSplitBytes) + 3);
+}
+
+struct JdState {
+  int32_t byte;  // < 0: no state
+  int32_t sub;   // bit | block << 3 | zigzag << 8
+};
+JD_HD bool jd_same(const JdState& a, const JdState& b) {
+  return a.byte == b.byte && a.sub == b.sub;
+}
+struct JdLaneSums {
+  JdState end;      // the first symbol that starts at or after the lane's boundary
+  int32_t nblk;     // DC symbols read = blocks this lane owns
+  uint32_t dc[3];   // their differences summed per component, wrapping
+};
+
+// blocks the serial walk decodes in interval k
+JD_HD int jd_interval_blocks(const JdInfo& I, int k) {
+  const int bpm = (I.hs & 3) * (I.vs & 3) + 2, mcus = I.mw * I.mh;
+  if (!I.ri) return mcus * bpm;
+  const long long left = (long long)mcus - (long long)k * I.ri;
+  return (int)(left < 0 ? 0 : left < I.ri ? left : I.ri) * bpm;
+}
+
+// where a lane whose subsequence begins at byte beg > istart starts before it knows better
+JD_HD JdState jd_lane_cold(const uint8_t* row, int istart, int beg) {
+  JdState s = {beg, 0};
+  if (beg > istart && row[beg - 1] == 0xff && row[beg] == 0) s.byte = beg + 1;
+  return s;
+}
+
+// the reader is certainly before row byte bound (cheap: stuffed bytes only move it back)
+JD_HD bool jd_reader_before(const JdReader& r, int bound) {
+  return r.bp - ((r.nbits + 7) >> 3) + r.pad < bound;
+}
+// the state at the reader's next bit; lo is the byte the reader started at; not overrun
+JD_HD JdState jd_reader_state(JdReader& r, int lo, int b, int k) {
+  const int nb = ((r.nbits + 7) >> 3) - r.pad;  // row bytes not wholly consumed, 0..8
+  int q = r.bp;
+  for (int i = 0; i < 8; ++i) {
+    if (i >= nb) break;
+    --q;
+    if (q > lo && r.byte_at(q) == 0u && r.byte_at(q - 1) == 0xffu) --q;
+  }
+  JdState s = {q < lo ? lo : q, ((8 - (r.nbits & 7)) & 7) | b << 3 | k << 8};
+  return s;
+}
+JD_HD JdReader jd_lane_reader(const uint8_t* row, int istart, int istop, const JdState& from,
+                              int& lo) {
+  lo = jd_clampi(from.byte, istart, istop);
+  JdReader r(row, lo, istop);
+  r.refill();
+  r.skip(from.sub & 7);
+  return r;
+}
+
+// One symbol at zigzag index k (0: DC).  Returns JD_SYM_ERR, or what it was, | JD_SYM_END when
+// it ended the block (k is 0 again): val is the DC difference or the coefficient at zigzag idx.
+enum : int { JD_SYM_ERR = -1, JD_SYM_DC = 0, JD_SYM_AC = 1, JD_SYM_RUN = 2, JD_SYM_END = 4 };
+JD_HD int jd_lane_symbol(JdReader& r, const JdHuff& dc, const JdHuff& ac, int& k, int& idx,
+                         int& val) {
+  if (k == 0) {
+    const int s = jd_symbol(r, dc);
+    if (s < 0 || s > 15) return JD_SYM_ERR;
+    val = s ? jd_receive_extend(r, s) : 0;
+    k = 1;
+    return JD_SYM_DC;
+  }
+  const int sym = jd_symbol(r, ac);
+  if (sym < 0) return JD_SYM_ERR;
+  const int run = sym >> 4, s = sym & 15;
+  if (s == 0) {
+    k = run == 15 ? k + 16 : 64;
+    if (k < 64) return JD_SYM_RUN;
+    k = 0;
+    return JD_SYM_RUN | JD_SYM_END;
+  }
+  k += run;
+  if (k > 63) return JD_SYM_ERR;
+  idx = k;
+  val = jd_receive_extend(r, s);
+  if (++k < 64) return JD_SYM_AC;
+  k = 0;
+  return JD_SYM_AC | JD_SYM_END;
+}
+
+// Speculate / decode again: walks the symbols from `from` up to the first one that starts at or
+// after row byte bound (<= istop) and sums what the lane would own.  Writes no pixels.  An
+// invalid code or running out of bits leaves o.end without a state; that is no error here.
+JD_HD void jd_lane_count(const uint8_t* row, const JdTables& t, int istart, int istop,
+                         const JdState& from, int bound, JdLaneSums& o) {
+  const JdInfo& I = t.info;
+  const int ny = (I.hs & 3) * (I.vs & 3), bpm = ny + 2;
+  o.end.byte = -1;
+  o.end.sub = 0;
+  o.nblk = 0;
+  o.dc[0] = o.dc[1] = o.dc[2] = 0u;
+  int lo, b = (from.sub >> 3) & 7, k = (from.sub >> 8) & 63;
+  if (b >= bpm) b = 0;
+  JdReader r = jd_lane_reader(row, istart, istop, from, lo);
+  if (r.overrun()) return;
+  for (int it = 0; it <= kJdSplitSymbols; ++it) {
+    if (!jd_reader_before(r, bound)) {
+      const JdState s = jd_reader_state(r, lo, b, k);
+      if (s.byte >= bound) {
+        o.end = s;
+        return;
+      }
+    }
+    const int c = b < ny ? 0 : b - ny + 1;
+    int idx = 0, val = 0;
+    const int kind = jd_lane_symbol(r, t.h[I.td[c] & 1], t.h[2 + (I.ta[c] & 1)], k, idx, val);
+    if (kind < 0 || r.overrun()) return;
+    if ((kind & 3) == JD_SYM_DC) {
+      ++o.nblk;
+      o.dc[c] += (uint32_t)val;
+    }
+    if (kind & JD_SYM_END) b = b + 1 == bpm ? 0 : b + 1;
+  }
+}
+
+// Write: the lane's verified state `from`, g = the interval-wide index of the first block it
+// owns, pred = the DC predictors there.  Decodes every block whose DC symbol starts before
+// bound, to its end, into coef[natural * stride] and through the IDCT into the planes; stops at
+// the interval's nblocks.  mcu0 is the interval's first MCU.  Returns 0, or 1 on anything the
+// serial walk would call an error (and on any bound below being hit): the caller hands the
+// interval back to the serial walk.
+JD_HD int jd_lane_write(const uint8_t* row, const JdTables& t, int istart, int istop,
+                        const JdState& from, int bound, int g, int nblocks, long long mcu0,
+                        const uint32_t (&pred0)[3], int16_t* coef, int stride, uint8_t* pl,
+                        long long pitch, long long plane_bytes) {
+  const JdInfo& I = t.info;
+  const int hs = I.hs & 3, vs = I.vs & 3, ny = hs * vs, bpm = ny + 2, mw = I.mw > 0 ? I.mw : 1;
+  int pred[3] = {(int)pred0[0], (int)pred0[1], (int)pred0[2]};
+  int lo, b = (from.sub >> 3) & 7, k = (from.sub >> 8) & 63;
+  if (b >= bpm || g < 0) return 1;
+  JdReader r = jd_lane_reader(row, istart, istop, from, lo);
+  int idx = 0, val = 0;
+  if (k != 0) {  // the tail of a block another lane owns
+    const int c = b < ny ? 0 : b - ny + 1;
+    for (int it = 0; it < 64 && k != 0; ++it)
+      if (jd_lane_symbol(r, t.h[I.td[c] & 1], t.h[2 + (I.ta[c] & 1)], k, idx, val) < 0) return 1;
+    if (k != 0) return 1;
+    b = b + 1 == bpm ? 0 : b + 1;
+  }
+  for (int blk = 0; blk < kJdSplitBlocks; ++blk) {
+    if (g >= nblocks) return 0;
+    if (r.overrun()) return 1;
+    if (!jd_reader_before(r, bound) && jd_reader_state(r, lo, b, 0).byte >= bound) return 0;
+    const int c = b < ny ? 0 : b - ny + 1;
+    const JdHuff& dc = t.h[I.td[c] & 1];
+    const JdHuff& ac = t.h[2 + (I.ta[c] & 1)];
+    for (int i = 0; i < 64; ++i) coef[i * stride] = 0;
+    int kind = 0;
+    for (int it = 0; it < 64; ++it) {
+      kind = jd_lane_symbol(r, dc, ac, k, idx, val);
+      if (kind < 0) return 1;
+      if ((kind & 3) == JD_SYM_DC) {
+        pred[c] = (int)((uint32_t)pred[c] + (uint32_t)val);
+        coef[0] = (int16_t)pred[c];
+      } else if ((kind & 3) == JD_SYM_AC) {
+        coef[kJdZigzag[idx & 63] * stride] = (int16_t)val;
+      }
+      if (kind & JD_SYM_END) break;
+    }
+    if (!(kind & JD_SYM_END) || r.overrun()) return 1;
+    const long long m = mcu0 + g / bpm;
+    const int mx = (int)(m % mw), myr = (int)(m / mw);
+    const int by = c == 0 ? myr * vs + b / hs : myr, bx = c == 0 ? mx * hs + b % hs : mx;
+    jd_idct_block(coef, stride, t.q[I.tq[c] & 3],
+                  pl + c * plane_bytes + (long long)by * 8 * pitch + bx * 8, pitch);
+    ++g;
+    b = b + 1 == bpm ? 0 : b + 1;
+  }
+  return 1;
 }
 
 }  // namespace kvedge

@@ -360,6 +360,21 @@ int kv_jpeg_decode_table_bytes(void);
 int kv_jpeg_decode(const unsigned char* files, unsigned char* tables, int* mpos,
                    unsigned char* planes, unsigned char* out, int* status, int N,
                    long long row_bytes, int H, int W, int lanes, hipStream_t s);
+// The same with long restart intervals decoded by one lane per kv_jpeg_decode_split_bytes()
+// bytes (four more launches between scan and decode: plan, speculate + synchronise, stitch,
+// write; whatever they cannot prove equal to the serial walk is handed back to it).  mode 0: as
+// kv_jpeg_decode; 1: intervals longer than sixteen subsequences; 2: longer than one.  Scratch on
+// top: split int32 [N, kv_jpeg_decode_split_ints(row_bytes)], done int32 [N, ceil(H/8) *
+// ceil(W/8)], paths int32 [N,2] = intervals the split launches completed / handed back.
+// launches = 7 for the whole op; fewer stops after that many of scan, plan, spec, stitch,
+// write, decode, colour and leaves the output incomplete (tools/jpeg_decode_probe.py times the
+// prefixes).  Returns -6 for another mode or count.
+int kv_jpeg_decode_split_bytes(void);
+long long kv_jpeg_decode_split_ints(long long row_bytes);
+int kv_jpeg_decode_split(const unsigned char* files, unsigned char* tables, int* mpos,
+                         unsigned char* planes, unsigned char* out, int* status, int* split,
+                         int* done, int* paths, int N, long long row_bytes, int H, int W,
+                         int lanes, int mode, int launches, hipStream_t s);
 // K4 fallback: y = x*scale[c] + shift[c] (+relu) on NHWC bf16.
 int kv_batchnorm_nhwc(const void* x, void* y, const float* scale, const float* shift,
                       int64_t rows, int C, int relu, hipStream_t s);

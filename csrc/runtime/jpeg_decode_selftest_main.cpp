@@ -6,9 +6,14 @@
 // ops.reference.jpeg_decode.  Every buffer is allocated at its exact size, so a read or write
 // past a row, a table or a plane is reported.
 //
-//   kv_jpeg_decode_selftest CORPUS OUT
+//   kv_jpeg_decode_selftest [--parallel G] CORPUS OUT
 //   CORPUS: int32 N, row_bytes, H, W, then N rows of row_bytes.  OUT: per file int32 status and
 //   H * W * 3 RGB bytes.
+//   --parallel G: every restart interval longer than one subsequence goes through the split
+//   path's lane steps (speculate, synchronise in groups of G lanes, seams, chain check, prefix
+//   sums, write) lane by lane, as the device's launches order them, and falls back to the serial
+//   walk on any anomaly; the result must equal the serial walk's (exit 7 if not) and is what
+//   OUT gets.  A small G puts seams into small files.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -21,8 +26,83 @@ using namespace kvedge;
 
 namespace {
 
-// what the scan / decode / colour launches do for one file, one interval after the other
-int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb) {
+constexpr int kSeamRounds = 8;
+
+// The split path for interval k = [istart, istop): true if it completed (the planes hold the
+// interval), false if it must be handed back.
+bool parallel_interval(const uint8_t* row, const JdTables& T, int k, int istart, int istop, int G,
+                       uint8_t* pl, long long pitch, long long plane) {
+  const int S = kJdSplitBytes, nl = (istop - 1) / S - istart / S + 1;
+  std::vector<int> beg(nl), bound(nl);
+  std::vector<JdState> from(nl);
+  std::vector<JdLaneSums> sums(nl);
+  for (int l = 0; l < nl; ++l) {
+    beg[l] = l ? (istart / S + l) * S : istart;
+    bound[l] = std::min((beg[l] / S + 1) * S, istop);
+    from[l] = jd_lane_cold(row, istart, beg[l]);
+  }
+  for (int g0 = 0; g0 < nl; g0 += G) {  // speculate + synchronise, one workgroup
+    const int ge = std::min(g0 + G, nl);
+    std::vector<char> need(nl, 1);
+    for (int r = 0; r < G; ++r) {
+      for (int l = g0; l < ge; ++l)
+        if (need[l]) jd_lane_count(row, T, istart, istop, from[l], bound[l], sums[l]);
+      bool any = false;
+      need[g0] = 0;
+      for (int l = g0 + 1; l < ge; ++l) {
+        const JdState prev = sums[l - 1].end;
+        need[l] = prev.byte >= 0 && !jd_same(prev, from[l]);
+        if (need[l]) from[l] = prev;
+        any |= need[l] != 0;
+      }
+      if (!any) break;
+    }
+  }
+  const int nwg = (nl + G - 1) / G;
+  for (int r = 0; r < kSeamRounds; ++r) {  // seams, odd then even
+    int moved = 0;
+    for (int half = 0; half < 2; ++half)
+      for (int s = 1 + half; s < nwg; s += 2) {
+        JdState e = sums[s * G - 1].end;
+        for (int l = s * G; l < std::min(s * G + G, nl) && e.byte >= 0; ++l) {
+          if (jd_same(from[l], e)) break;
+          jd_lane_count(row, T, istart, istop, e, bound[l], sums[l]);
+          from[l] = e;
+          e = sums[l].end;
+          ++moved;
+        }
+      }
+    if (!moved) break;
+  }
+  int g = 0;  // chain check and prefix sums
+  uint32_t pred[3] = {0, 0, 0};
+  std::vector<int> g0s(nl);
+  std::vector<uint32_t> preds((size_t)nl * 3);
+  for (int l = 0; l < nl; ++l) {
+    const JdState want = l ? sums[l - 1].end : JdState{istart, 0};
+    if (want.byte < 0 || !jd_same(from[l], want)) return false;
+    g0s[l] = g;
+    g += sums[l].nblk;
+    for (int c = 0; c < 3; ++c) {
+      preds[(size_t)l * 3 + c] = pred[c];
+      pred[c] += sums[l].dc[c];
+    }
+  }
+  if (g != jd_interval_blocks(T.info, k)) return false;
+  bool ok = true;
+  int16_t coef[64];
+  for (int l = 0; l < nl; ++l) {
+    const uint32_t p[3] = {preds[(size_t)l * 3], preds[(size_t)l * 3 + 1], preds[(size_t)l * 3 + 2]};
+    ok &= !jd_lane_write(row, T, istart, istop, from[l], bound[l], g0s[l],
+                         jd_interval_blocks(T.info, k), (long long)k * T.info.ri, p, coef, 1, pl,
+                         pitch, plane);
+  }
+  return ok;
+}
+
+// what the scan / decode / colour launches do for one file, one interval after the other;
+// G > 0: long intervals try the split path first.  paths: completed, handed back.
+int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb, int G, int (&paths)[2]) {
   JdTables* T = static_cast<JdTables*>(aligned_alloc(16, sizeof(JdTables)));
   memset(T, 0, sizeof(JdTables));
   int err = jd_parse_header(row, n, H, W, T);
@@ -31,7 +111,7 @@ int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb) {
     free(T);
     return -err;
   }
-  const JdInfo& I = T->info;
+  JdInfo& I = T->info;
   std::vector<int> mpos;
   bool eoi = false;
   for (int i = I.e0; i + 1 < n; ++i) {
@@ -45,6 +125,9 @@ int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb) {
   }
   const int nmark = (int)mpos.size(), present = eoi ? nmark : nmark + 1;
   err = (eoi ? 0 : JD_E_NOEOI) | (present != I.expected ? JD_E_INTERVALS : 0);
+  I.nmark = nmark;
+  I.present = present;
+  mpos.resize((size_t)std::max(nmark, I.expected) + 1, 0);
 
   const long long pitch = (W + 15) / 16 * 16, plane = pitch * ((H + 15) / 16 * 16);
   uint8_t* pl = static_cast<uint8_t*>(aligned_alloc(16, (size_t)(3 * plane)));
@@ -55,10 +138,12 @@ int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb) {
     bool failed = k >= present;
     int start = 0, stop = 0;
     if (!failed) {
-      start = k == 0 ? I.e0 : mpos[k - 1] + 2;
-      stop = k < nmark ? mpos[k] : n;
-      if (start > n) start = n;
-      if (stop < start) stop = start;
+      jd_interval(I, mpos.data(), k, n, (int)mpos.size(), start, stop);
+      if (G > 0 && stop - start > kJdSplitBytes) {
+        const bool ok = parallel_interval(row, *T, k, start, stop, G, pl, pitch, plane);
+        ++paths[ok ? 0 : 1];
+        if (ok) continue;
+      }
     }
     JdReader rd(row, start, stop);
     int pred[3] = {0, 0, 0};
@@ -106,8 +191,15 @@ int decode_file(const uint8_t* row, int n, int H, int W, uint8_t* rgb) {
 }  // namespace
 
 int main(int argc, char** argv) {
+  int G = 0;
+  if (argc == 5 && !strcmp(argv[1], "--parallel")) {
+    G = atoi(argv[2]);
+    argv += 2;
+    argc -= 2;
+    if (G < 1 || G > 1024) return 2;
+  }
   if (argc != 3) {
-    fprintf(stderr, "usage: %s CORPUS OUT\n", argv[0]);
+    fprintf(stderr, "usage: %s [--parallel G] CORPUS OUT\n", argv[0]);
     return 2;
   }
   FILE* f = fopen(argv[1], "rb");
@@ -118,16 +210,23 @@ int main(int argc, char** argv) {
   FILE* o = fopen(argv[2], "wb");
   if (!o) return 5;
   uint8_t* row = static_cast<uint8_t*>(aligned_alloc(16, (size_t)n));  // exactly one row
-  std::vector<uint8_t> rgb((size_t)H * W * 3);
+  std::vector<uint8_t> rgb((size_t)H * W * 3), serial(rgb.size());
+  int paths[2] = {0, 0}, none[2] = {0, 0}, differ = 0;
   for (int i = 0; i < N; ++i) {
     if (fread(row, 1, (size_t)n, f) != (size_t)n) return 6;
-    const int32_t st = decode_file(row, n, H, W, rgb.data());
+    const int32_t st = decode_file(row, n, H, W, rgb.data(), G, paths);
+    if (G && (decode_file(row, n, H, W, serial.data(), 0, none) != st || serial != rgb)) {
+      fprintf(stderr, "file %d: the split path and the serial walk differ\n", i);
+      ++differ;
+    }
     fwrite(&st, 4, 1, o);
     fwrite(rgb.data(), 1, rgb.size(), o);
   }
   free(row);
   fclose(o);
   fclose(f);
-  printf("jpeg_decode selftest: %d files decoded\n", N);
-  return 0;
+  printf("jpeg_decode selftest: %d files decoded", N);
+  if (G) printf(", split path completed %d intervals, handed back %d", paths[0], paths[1]);
+  printf("\n");
+  return differ ? 7 : 0;
 }

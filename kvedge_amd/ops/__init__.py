@@ -2565,6 +2565,11 @@ def jpeg_encode(images: torch.Tensor, enc: JpegEncoder, out: Optional[torch.Tens
 JPEG_DECODE_ERRORS = _ref.JPEG_DECODE_ERRORS
 JPEG_DECODE_TABLE_BYTES = 6256  # sizeof(JdTables), csrc/kernels/jpeg_decode_core.h
 JPEG_DECODE_LANES = (16, 32, 64)
+JPEG_DECODE_ENTROPY = ("serial", "auto", "parallel")  # the native op's mode 0 / 1 / 2
+# S: a long restart interval is cut at the row's multiples of S into one lane each
+# (kJdSplitBytes, csrc/kernels/jpeg_decode_core.h).  "parallel" splits intervals longer than S,
+# "auto" those longer than 16 S (kJdAutoSplitBytes: the measured crossover, docs/kernels.md K29).
+JPEG_DECODE_SPLIT_BYTES = 64
 
 
 def jpeg_row_bytes(hw) -> int:
@@ -2582,10 +2587,23 @@ class JpegDecoder:
     ``planes`` uint8 [streams, 3, H16, W16] (the Y / Cb / Cr samples before upsampling, H16 /
     W16 = H / W rounded up to 16) and ``status`` int32 [streams].  The op allocates nothing.
     ``lanes``: restart intervals per wavefront of the decode launch (16, 32 or 64); fewer
-    lanes give more wavefronts when streams x intervals is small."""
+    lanes give more wavefronts when streams x intervals is small.
+
+    ``entropy``: who decodes a long restart interval (a file without restart markers is one).
+    ``"serial"``: one lane, as every short interval; ``"parallel"``: one lane per
+    JPEG_DECODE_SPLIT_BYTES of every interval longer than that; ``"auto"``: of every interval
+    longer than sixteen times that; fixed when the decoder is made.  The split launches keep their
+    lanes in ``split`` int32 [streams, 16 + 10 * L] with L = 3 * (row_bytes //
+    JPEG_DECODE_SPLIT_BYTES) + 3 lanes (the size is the native library's; header: lanes in use,
+    most synchronisation rounds of a workgroup, seam rounds, seam passes, then 12 counts of
+    workgroups by their synchronisation rounds, 11 and more in the last), mark
+    every interval in ``done`` int32 [streams, like mpos] (0 left to the serial walk, 1 completed,
+    2 handed back to it) and count them in ``paths`` int32 [streams, 2] = (completed, handed
+    back).  The CPU reference ignores ``entropy``; ``paths`` stays zero there and with
+    ``"serial"``."""
 
     def __init__(self, streams: int, hw, row_bytes: Optional[int] = None, device="cpu",
-                 lanes: int = 16):
+                 lanes: int = 16, entropy: str = "auto"):
         h, w = int(hw[0]), int(hw[1])
         if not (1 <= h <= JPEG_MAX_EXTENT and 1 <= w <= JPEG_MAX_EXTENT):
             raise ValueError(f"JPEG image size {h}x{w} outside 1..{JPEG_MAX_EXTENT}")
@@ -2596,9 +2614,14 @@ class JpegDecoder:
             raise ValueError(f"row_bytes must be a multiple of 16 in 16..2^31-16, got {row_bytes}")
         if lanes not in JPEG_DECODE_LANES:
             raise ValueError(f"lanes must be one of {JPEG_DECODE_LANES}, got {lanes!r}")
+        if entropy not in JPEG_DECODE_ENTROPY:
+            raise ValueError(f"entropy must be one of {JPEG_DECODE_ENTROPY}, got {entropy!r}")
         self.streams, self.hw, self.row_bytes, self.lanes = int(streams), (h, w), row_bytes, lanes
+        self._entropy = entropy
         dev = torch.device(device)
         self.status = torch.zeros(self.streams, dtype=torch.int32, device=dev)
+        self.paths = torch.zeros(self.streams, 2, dtype=torch.int32, device=dev)
+        self.split = self.done = None
         if dev.type == "cuda":
             h16, w16 = -(-h // 16) * 16, -(-w // 16) * 16
             self.tables = torch.zeros(self.streams, JPEG_DECODE_TABLE_BYTES, dtype=torch.uint8,
@@ -2606,12 +2629,21 @@ class JpegDecoder:
             self.mpos = torch.zeros(self.streams, -(-h // 8) * -(-w // 8), dtype=torch.int32,
                                     device=dev)
             self.planes = torch.zeros(self.streams, 3, h16, w16, dtype=torch.uint8, device=dev)
+            if entropy != "serial":
+                self.split = torch.zeros(self.streams,
+                                         _native().jpeg_decode_split_ints(row_bytes),
+                                         dtype=torch.int32, device=dev)
+                self.done = torch.zeros_like(self.mpos)
         else:
             self.tables = self.mpos = self.planes = None  # the reference needs none
 
     @property
     def device(self) -> torch.device:
         return self.status.device
+
+    @property
+    def entropy(self) -> str:
+        return self._entropy
 
 
 def jpeg_decode(files: torch.Tensor, dec: JpegDecoder, out: Optional[torch.Tensor] = None,
@@ -2623,8 +2655,10 @@ def jpeg_decode(files: torch.Tensor, dec: JpegDecoder, out: Optional[torch.Tenso
     truncated header) zero-fills the image; an entropy error zeroes the rest of its restart
     interval.  What is accepted and every rule is written out at ops.reference.jpeg_decode; GPU
     and CPU agree byte for byte, status and malformed files included.  Three launches on the
-    current stream (csrc/kernels/jpeg_decode.hip), no allocation when ``out`` is given, no host
-    synchronisation, capturable.  File n works in row ``slot0 + n`` of the decoder's scratch."""
+    current stream (csrc/kernels/jpeg_decode.hip), seven unless ``dec.entropy`` is "serial" (the
+    split launches for long restart intervals, which also write ``dec.paths``); no allocation
+    when ``out`` is given, no host synchronisation, capturable.  File n works in row
+    ``slot0 + n`` of the decoder's scratch."""
     if not isinstance(dec, JpegDecoder):
         raise TypeError(f"dec must be an ops.JpegDecoder, got {type(dec).__name__}")
     if (files.dtype != torch.uint8 or files.dim() != 2 or files.shape[1] != dec.row_bytes
@@ -2647,7 +2681,11 @@ def jpeg_decode(files: torch.Tensor, dec: JpegDecoder, out: Optional[torch.Tenso
         raise ValueError(f"out must be contiguous uint8 [{n}, {h}, {w}, 3] on {files.device}")
     rows = slice(slot0, slot0 + n)
     status = dec.status[rows]
-    if files.is_cuda:
+    if files.is_cuda and dec.entropy != "serial":
+        _native().jpeg_decode_split(files, dec.tables[rows], dec.mpos[rows], dec.planes[rows],
+                                    out, status, dec.split[rows], dec.done[rows], dec.paths[rows],
+                                    dec.lanes, JPEG_DECODE_ENTROPY.index(dec.entropy), 7)
+    elif files.is_cuda:
         _native().jpeg_decode(files, dec.tables[rows], dec.mpos[rows], dec.planes[rows], out,
                               status, dec.lanes)
     else:
